@@ -28,7 +28,13 @@ population.  Two schedules of that same input are timed back to back in one run:
   across ranks every step (reduce-scatter -> Adam on the owned 1/N slice -> all-gather,
   ZeRO-1, the same bytes as one all-reduce) by the two-shot xGMI exchange or RCCL.
 
-Usage: ``python bench.py [--gpus N] [--steps K] [--warmup W]``.  With ``--gpus N > 1`` and no
+Usage: ``python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]``.
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds
+what takes a run of its own after the timed region (today: the count of device operations of
+one steady-state step under torch.profiler, ``config.device_ops_per_step``).
+``--dump-outputs DIR`` writes what the last timed step computed (the parameters after it and
+its loss) as ``DIR/<name>.npy``; the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.  With ``--gpus N > 1`` and no
 launcher environment the script starts ``torch.distributed.run`` with N ranks itself
 (before any GPU call in this process) and relays rank 0's JSON line; under a launcher
 (``WORLD_SIZE`` set) it runs as one rank.
@@ -90,9 +96,14 @@ def _args(argv=None):
                          "is unbounded")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--profile-phases", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the count of the "
+                         "device operations of one step (torch.profiler, after the timed region)")
     ap.add_argument("--no-count-launches", dest="count_launches", action="store_false",
-                    help="skip counting the device operations of one step (torch.profiler, "
-                         "after the timed region)")
+                    help="with --full: skip counting the device operations of one step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the outputs of the last one (params, "
+                         "loss) as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -156,7 +167,29 @@ def bench_bounds(args, data):
     return pb
 
 
-def time_placement(placement, args, comm, dev, sync):
+DUMP_MAX_BYTES = 48 << 20  # per array; all arrays of one dump stay under 64 MB
+
+
+def dump_outputs(path, engine, comm):
+    """Write what the last timed step computed -- the parameters after it (what ``run_adam``
+    returns as the last trajectory row) and its loss -- as ``path/<name>.npy`` (rank 0;
+    collective: the parameters are assembled across ranks).  A parameter vector above
+    ``DUMP_MAX_BYTES`` is written as a fixed, seeded sample of its elements."""
+    import numpy as np
+    theta = engine.params().detach().float().cpu().numpy()
+    loss = np.asarray([engine.last_loss()], dtype=np.float64)
+    if comm.rank != 0:
+        return
+    keep = DUMP_MAX_BYTES // theta.itemsize
+    if theta.size > keep:
+        idx = np.sort(np.random.default_rng(20240607).choice(theta.size, keep, replace=False))
+        theta = theta[idx]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "params.npy"), np.ascontiguousarray(theta, dtype=np.float32))
+    np.save(os.path.join(path, "loss.npy"), loss)
+
+
+def time_placement(placement, args, comm, dev, sync, dump=None):
     """Build the data and engine for one placement, warm up, time ``args.steps`` steps.
 
     Returns the per-rank record (elapsed is the MAX over ranks)."""
@@ -181,7 +214,7 @@ def time_placement(placement, args, comm, dev, sync):
     if args.profile_phases:  # HIP-event timing per phase (eager launches)
         from multigrad_amd.utils.profiling import PhaseTimer
         engine.timer = PhaseTimer(True)
-    count = args.count_launches and dev.type == "cuda"
+    count = args.full and args.count_launches and dev.type == "cuda"
     engine.setup(data["guess"], nsteps=args.warmup + args.steps + (2 if count else 0),
                  learning_rate=args.lr, history=history, param_bounds=bench_bounds(args, data))
     sync()
@@ -223,6 +256,8 @@ def time_placement(placement, args, comm, dev, sync):
     engine.check()  # a failed peer exchange raises here instead of reporting wrong numbers
     loss1 = engine.last_loss()
     fb = model.lane_fallback_groups(data["guess"])  # lane groups on the per-edge path
+    if dump:  # the state after exactly warmup + steps steps, before any further step
+        dump_outputs(dump, engine, comm)
     ops = {}
     if count:  # after the timing: device operations of one steady-state step
         from multigrad_amd.utils.profiling import count_device_ops
@@ -334,8 +369,11 @@ def main(argv=None):
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
 
-    res, errors = run_placements(order, lambda p: time_placement(p, args, comm, dev, sync),
-                                 on_error=release)
+    # --dump-outputs writes the headline placement's outputs
+    res, errors = run_placements(
+        order, lambda p: time_placement(p, args, comm, dev, sync,
+                                        dump=args.dump_outputs if p == order[0] else None),
+        on_error=release)
     head = res[order[0]]
     dense = res.get("hashed", head if comm.size == 1 else None)
     history = head["history"]

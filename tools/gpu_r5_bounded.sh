@@ -16,10 +16,10 @@ timeout -k 10 900 python -u -m pytest -x -v --timeout 300 --timeout-method threa
   "tests/test_twoshot_gpu.py::test_engine_hashed_fused_exchange_matches_serial" \
   > $O/pytest.log 2>&1 || { tail -60 $O/pytest.log; exit 1; }
 tail -3 $O/pytest.log
-timeout -k 10 300 python -u bench.py --steps 200 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
-timeout -k 10 300 python -u bench.py --steps 200 --warmup 5 --bounds both > $O/bench_bounds_both.json 2> $O/bench_bb.err || { tail -20 $O/bench_bb.err; exit 1; }
-MULTIGRAD_PIPELINE=0 timeout -k 10 300 python -u bench.py --steps 200 --warmup 5 --bounds both > $O/bench_bounds_both_unpipelined.json 2> $O/bench_bbu.err || { tail -20 $O/bench_bbu.err; exit 1; }
-timeout -k 10 300 python -u bench.py --steps 200 --warmup 5 --bounds mixed > $O/bench_bounds_mixed.json 2> $O/bench_bm.err || { tail -20 $O/bench_bm.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --steps 200 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --steps 200 --warmup 5 --bounds both > $O/bench_bounds_both.json 2> $O/bench_bb.err || { tail -20 $O/bench_bb.err; exit 1; }
+MULTIGRAD_PIPELINE=0 timeout -k 10 300 python -u bench.py --full --steps 200 --warmup 5 --bounds both > $O/bench_bounds_both_unpipelined.json 2> $O/bench_bbu.err || { tail -20 $O/bench_bbu.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --steps 200 --warmup 5 --bounds mixed > $O/bench_bounds_mixed.json 2> $O/bench_bm.err || { tail -20 $O/bench_bm.err; exit 1; }
 for f in $O/bench_*.json; do python -c "import json,sys; d=json.load(open('$f')); print('$f', d['value'], d['ms_per_step'], d['config']['pipelined'], d['config']['device_ops_per_step'])"; done
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/prof -o bb -- \
