@@ -6,7 +6,7 @@
 #include <vector>
 
 namespace mg {
-// smf.hip
+// smf_tiles.hip, smf_lanes.hip, smf2.hip
 int smf_padded_bins(int64_t nb);
 int64_t smf_fwd_max_blocks(int64_t nb, bool log_sigma, bool has_pop, bool rel_tail);
 void smf_forward(torch::Tensor x, c10::optional<torch::Tensor> pop, torch::Tensor theta,

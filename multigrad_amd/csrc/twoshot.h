@@ -1,7 +1,7 @@
 // Two-shot reduce-scatter -> Adam -> all-gather over peer memory (see xgmi.hip for the
 // protocol), as the work of a range of workgroups: the stand-alone exchange kernel
 // (xgmi.hip) and the compute kernels that run the exchange of the previous parameter chunk
-// in their first workgroups (smf.hip, "fused exchange": the exchange of chunk c-1 overlaps
+// in their first workgroups (smf_tiles.hip, "fused exchange": the exchange of chunk c-1 overlaps
 // the VJP of chunk c without a second stream or cross-stream events).
 #pragma once
 
@@ -193,7 +193,7 @@ __device__ __forceinline__ void twoshot_block(const TwoShotArgs& a, int bid, int
 
 // The exchange carried by a compute kernel (fused exchange), peers 4 at a time: unbounded
 // Adam (mode 1), or bounded (mode 2, or 3 with the legacy Jacobian) in the kernels' separate
-// bounded instantiations (XS = 2 in smf.hip), so the unbounded ones keep their registers.
+// bounded instantiations (XS = 2 in smf_tiles.hip), so the unbounded ones keep their registers.
 __device__ __forceinline__ void twoshot_block_fused(const TwoShotArgs& a, int bid, int nblk,
                                                     int* lds) {
   twoshot_block<1, 4>(a, bid, nblk, lds);

@@ -1,6 +1,6 @@
 // Device side of the one-shot peer-memory all-reduce (see xgmi.hip for the protocol).
 // Shared by the stand-alone all-reduce kernel and by kernels that fuse the exchange into
-// their epilogue (smf.hip: slab reduction -> exchange -> loss in one launch).
+// their epilogue (smf_tiles.hip: slab reduction -> exchange -> loss in one launch).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -354,7 +354,7 @@ void xgmi_twoshot_launch_packed(std::string packed) {
 }
 
 // The same step's arguments packed as bytes, for a compute launch that runs the exchange
-// in its first workgroups (smf.hip fused exchange: smf_forward / smf_vjp ``exchange``);
+// in its first workgroups (smf_tiles.hip fused exchange: smf_forward / smf_vjp ``exchange``);
 // Adam modes only.  The tensors must stay alive until that launch is enqueued.
 pybind11::bytes xgmi_twoshot_pack(std::vector<int64_t> gbufs, std::vector<int64_t> tbufs,
                                   std::vector<int64_t> flags, int64_t rank, int64_t lo, int64_t n,

@@ -1304,7 +1304,7 @@ class FusedAdamEngine:
                     and (self.size == 1 or self.oneshot is not None) and self.slab.is_cuda)
         advance = None
         # the last chunk's forward host call also issues the epilogue launch (one host call
-        # per step fewer; ops/smf.py:smf_forward_into, csrc/smf.hip:smf_forward_lanes)
+        # per step fewer; ops/smf.py:smf_forward_into, csrc/smf_lanes.hip:smf_forward_lanes)
         fold = fused_ok and _env_flag("MULTIGRAD_FOLD_EPILOGUE", True) and \
             getattr(md, "engine_forward_epilogue_ok", lambda: False)()
         chunks = [self.rank] if self.owner else list(range(self.C))

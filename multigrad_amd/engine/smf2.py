@@ -6,7 +6,7 @@ smf_gradient_descent.py:19-91 (``DocsSMFModel``), driven by ``run_simple_grad_de
 (multigrad/util.py:80-134, the path timed by tests/smf_example/benchmark.py:10-46) or
 ``run_adam`` (multigrad/adam.py:52-68).
 
-A step is the kernels of ``csrc/smf.hip`` "shared-parameter fused step": ONE pass over the
+A step is the kernels of ``csrc/smf2.hip``: ONE pass over the
 halos yields, per edge, the bin masses and the two VJP residual sums, and because both
 parameters are shared by every halo the gradient is linear in those sums -- so the sumstat
 all-reduce and the gradient all-reduce of the reference (multigrad/multigrad.py:522,531-532)

@@ -377,7 +377,7 @@ class PopulationSMFModel(OnePointModel):
         """Group the lanes by forward path at ``guess`` (user-order parameters; called by the
         fused engine before :meth:`engine_set_chunks`, at setup and when it re-lays the lanes
         out during a fit): populations whose bin width exceeds the Euler-Maclaurin range
-        (h = delta / sigma > 0.5, csrc/smf.hip kEmHMax) get lane groups of their own, so a
+        (h = delta / sigma > 0.5, csrc/smf_device.h kEmHMax) get lane groups of their own, so a
         few narrow populations do not send whole groups to the per-edge path.  Returns
         whether the classes changed.  ``MULTIGRAD_LANE_CLASSES=0`` turns it off."""
         sh = self.shard

@@ -8,7 +8,7 @@
   with ``sigma = 10**log_sigma`` and ``+1e-10`` inside the logs.
 
 On a GPU the sumstats come from the fused HIP kernel (all bins in one pass over the
-halos, ``csrc/smf.hip``); on CPU from the equivalent PyTorch expression.  Halos are
+halos, ``csrc/smf_tiles.hip``); on CPU from the equivalent PyTorch expression.  Halos are
 sharded across ranks with ``array_split`` exactly as in the reference, so the summed
 sumstats are partition invariant.
 """

@@ -1,6 +1,6 @@
 """SMF summed-statistic ops: HIP forward/VJP kernels + fp32/fp64 PyTorch references.
 
-Device tensors run ``csrc/smf.hip`` (one pass over the halos for all bins, deterministic
+Device tensors run ``csrc/smf_tiles.hip`` and ``csrc/smf_lanes.hip`` (one pass over the halos for all bins, deterministic
 reductions, segmented per-population VJP).  CPU tensors use the PyTorch formulation
 below, which is also the numerics oracle for the kernel tests.
 """
@@ -61,7 +61,7 @@ class SmfBins:
     @property
     def delta(self) -> float:
         """Edge spacing when the edges are uniformly spaced (the Euler-Maclaurin forward's
-        condition, csrc/smf.hip make_bins), else 0."""
+        condition, csrc/smf_host.h make_bins), else 0."""
         e = np.asarray(self.edges, dtype=np.float64)
         d = (e[-1] - e[0]) / max(len(e) - 1, 1)
         ok = d > 0 and np.all(np.abs(e - (e[0] + d * np.arange(len(e)))) <=
@@ -355,7 +355,7 @@ class PopulationShard:
         (runtime.cpp:lpt_waves); ``dynamic`` -- 256 device work queues drawn by atomic
         tickets (waves that the oldest-first issue arbitration favours take more groups);
         ``0`` -- grid-stride over the longest-first order; ``auto`` (default) -- static.
-        The static lists run with issue-priority feedback (``MG_FWD_PRIO`` in smf.hip: a
+        The static lists run with issue-priority feedback (``MG_FWD_PRIO`` in smf_lanes.hip: a
         wave's priority falls as its list drains), which removes most of the
         oldest-wave-first tail.  Until round 5 ``auto`` took the dynamic queues when every
         wave got >= 8 groups (the headline); round 6 measured static faster at every size

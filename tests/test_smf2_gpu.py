@@ -1,4 +1,4 @@
-"""Fused step of the shared-parameter SMF models (csrc/smf.hip "shared-parameter fused
+"""Fused step of the shared-parameter SMF models (csrc/smf2.hip "shared-parameter fused
 step", engine/smf2.py) on the MI355X, against fp64 PyTorch oracles of the same math and
 the reference's golden values (reference tests/test_mpi.py,
 docs/source/notebooks/intro.ipynb:209-214)."""

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Device assembly of one csrc/*.hip file for gfx950 (extra -D flags pass through), plus a
-# per-kernel instruction census of the main loop: bash tools/isa.sh smf [-DMG_X=1 ...]
+# per-kernel instruction census of the main loop: bash tools/isa.sh smf_lanes [-DMG_X=1 ...]
 set -eu
 R=$(cd "$(dirname "$0")/.." && pwd)
 src=$1; shift
