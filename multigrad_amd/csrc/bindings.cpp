@@ -119,6 +119,11 @@ void multi_dot(torch::Tensor A, int64_t nrows, std::vector<torch::Tensor> B, int
 int64_t multi_dot_workspace(int64_t nrows, int64_t n);
 void lincomb(torch::Tensor H, int64_t nrows, torch::Tensor coef, double alpha,
              c10::optional<torch::Tensor> x, int64_t n, torch::Tensor y);
+void lincomb_cols(torch::Tensor H, int64_t nrows, torch::Tensor coef, double alpha,
+                  c10::optional<torch::Tensor> x, c10::optional<torch::Tensor> pre,
+                  c10::optional<torch::Tensor> post, int64_t n, torch::Tensor y);
+void compact_diag(torch::Tensor H, torch::Tensor rows, torch::Tensor fac, torch::Tensor Q,
+                  double h0, c10::optional<torch::Tensor> scale, int64_t n, torch::Tensor out);
 // runtime.cpp
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int64_t>
 build_tiles(torch::Tensor counts, std::vector<int64_t> breaks, int64_t tile_halos,
@@ -214,6 +219,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("multi_dot", &mg::multi_dot);
   m.def("multi_dot_workspace", &mg::multi_dot_workspace);
   m.def("lincomb", &mg::lincomb);
+  m.def("lincomb_cols", &mg::lincomb_cols);
+  m.def("compact_diag", &mg::compact_diag);
   m.def("build_tiles", &mg::build_tiles);
   m.def("sort_by_population", &mg::sort_by_population);
   m.def("build_lanes", &mg::build_lanes, pybind11::arg("counts"), pybind11::arg("breaks"),

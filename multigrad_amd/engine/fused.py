@@ -2060,6 +2060,11 @@ class _EngineObjective:
         r, _, k = spec.partition(":")
         return int(r) == self.e.rank and int(k or 1) == self._nev
 
+    def vector_layout(self) -> "_EngineLayout":
+        """The mapping between the user's parameter order and this objective's vector, as
+        it stands now (it owns what it needs: usable after the engine is closed)."""
+        return _EngineLayout(self.e)
+
     def full(self, x: torch.Tensor) -> torch.Tensor:
         """The full parameter vector (model order) for the optimizer's vector x."""
         self._load(x)
@@ -2067,3 +2072,78 @@ class _EngineObjective:
         if self.e.owner:
             return self.e.params().clone()
         return self.e.to_user(self.e.theta[:self.e.P]).clone()
+
+
+class _EngineLayout:
+    """User parameter order <-> the vector of an :class:`_EngineObjective` (last dimension;
+    leading batch dimensions allowed in both directions).
+
+    Replicated: permute to the internal order and pad.  Owner placement: permute and take
+    the owned range; back by an all-gather of equal padded pieces (as
+    ``FusedAdamEngine._assemble``).  ZeRO: the owned slice of every chunk, concatenated; back
+    by one all-gather of the local vectors, placed chunk by chunk.  Padding entries are zero
+    in every optimizer vector, so they drop out.  It never touches ``engine.theta`` and owns
+    (copies of) the index data it needs, so it works after the engine is closed or re-laid
+    out; on several ranks ``from_local`` is collective."""
+
+    def __init__(self, eng: "FusedAdamEngine"):
+        self.comm, self.size, self.rank = eng.comm, eng.size, eng.rank
+        self.device = eng.device
+        self.P, self.P_pad = int(eng.P), int(eng.P_pad)
+        self.pidx = None if eng.pidx is None else eng.pidx.clone()
+        self.inv_pidx = None if eng.pidx is None else eng.inv_pidx.clone()
+        self.pb, self.lengths = list(eng.pb), list(eng.lengths)
+        self.owner, self.zero = bool(eng.owner), bool(eng.zero) and not eng.owner
+        if self.owner:
+            self.own_range = tuple(eng.own_range)
+            self.n_local = self.own_range[1] - self.own_range[0]
+        elif self.zero:
+            self.own = [tuple(o) for o in eng.own]
+            self.loc_off, self.loc_len = list(eng.loc_off), list(eng.loc_len)
+            self.n_local = sum(self.loc_len)
+        else:
+            self.n_local = self.P_pad
+
+    def to_local(self, v: torch.Tensor) -> torch.Tensor:
+        v = v.to(self.device)
+        if self.pidx is not None:
+            v = v[..., self.pidx]
+        if self.P_pad > self.P:
+            v = torch.cat([v, v.new_zeros(v.shape[:-1] + (self.P_pad - self.P,))], -1)
+        if self.owner:
+            a, b = self.own_range
+            v = v[..., a:b]
+        elif self.zero:
+            v = torch.cat([v[..., a:b] for a, b in self.own], -1)
+        return v.contiguous()
+
+    def from_local(self, t: torch.Tensor) -> torch.Tensor:
+        lead = tuple(t.shape[:-1])
+        if self.owner:
+            L = max(self.lengths)
+            buf = torch.zeros(lead + (L,), dtype=t.dtype, device=t.device)
+            buf[..., :t.shape[-1]] = t
+            gathered = self._gather(buf)
+            full = torch.empty(lead + (self.P_pad,), dtype=t.dtype, device=t.device)
+            for r in range(self.size):
+                a, b = self.pb[r], self.pb[r + 1]
+                full[..., a:b] = gathered[r][..., :b - a]
+        elif self.zero:
+            gathered = self._gather(t.contiguous())
+            full = torch.empty(lead + (self.P_pad,), dtype=t.dtype, device=t.device)
+            for c, (o, n) in enumerate(zip(self.loc_off, self.loc_len)):
+                for r in range(self.size):
+                    a = self.pb[c] + r * n
+                    full[..., a:a + n] = gathered[r][..., o:o + n]
+        else:
+            full = t
+        full = full[..., :self.P]
+        return full[..., self.inv_pidx] if self.inv_pidx is not None else full.clone()
+
+    def _gather(self, piece: torch.Tensor) -> torch.Tensor:
+        """``[W, *piece.shape]``: every rank's (equally shaped) piece in rank order."""
+        if self.size == 1:
+            return piece.reshape((1,) + tuple(piece.shape))
+        out = torch.empty((self.size,) + tuple(piece.shape), dtype=piece.dtype, device=piece.device)
+        self.comm.all_gather_into_tensor(out.reshape(-1), piece.reshape(-1))
+        return out
