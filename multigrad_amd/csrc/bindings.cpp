@@ -124,6 +124,12 @@ void lincomb_cols(torch::Tensor H, int64_t nrows, torch::Tensor coef, double alp
                   c10::optional<torch::Tensor> post, int64_t n, torch::Tensor y);
 void compact_diag(torch::Tensor H, torch::Tensor rows, torch::Tensor fac, torch::Tensor Q,
                   double h0, c10::optional<torch::Tensor> scale, int64_t n, torch::Tensor out);
+// binned.hip
+torch::Tensor binned_forward(torch::Tensor mu, torch::Tensor sigma, c10::optional<torch::Tensor> w,
+                             std::vector<double> edges);
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> binned_backward(
+    torch::Tensor mu, torch::Tensor sigma, c10::optional<torch::Tensor> w, std::vector<double> edges,
+    torch::Tensor g, bool need_mu, bool need_sigma, bool need_w);
 // runtime.cpp
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int64_t>
 build_tiles(torch::Tensor counts, std::vector<int64_t> breaks, int64_t tile_halos,
@@ -221,6 +227,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("lincomb", &mg::lincomb);
   m.def("lincomb_cols", &mg::lincomb_cols);
   m.def("compact_diag", &mg::compact_diag);
+  m.def("binned_forward", &mg::binned_forward);
+  m.def("binned_backward", &mg::binned_backward);
   m.def("build_tiles", &mg::build_tiles);
   m.def("sort_by_population", &mg::sort_by_population);
   m.def("build_lanes", &mg::build_lanes, pybind11::arg("counts"), pybind11::arg("breaks"),

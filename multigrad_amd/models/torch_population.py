@@ -14,10 +14,12 @@ from dataclasses import dataclass
 
 import torch
 
+from ..ops.binned import gaussian_binned_sum
 from ..ops.smf import logmse_loss
 from .onepoint import OnePointModel
 
-__all__ = ["TorchPopulationSMFModel", "StochasticTorchPopulationSMFModel", "torch_population_data"]
+__all__ = ["TorchPopulationSMFModel", "StochasticTorchPopulationSMFModel",
+           "BinnedPopulationSMFModel", "torch_population_data"]
 
 
 def torch_population_data(data: dict) -> dict:
@@ -73,3 +75,23 @@ class StochasticTorchPopulationSMFModel(TorchPopulationSMFModel):
             x = x + self.scatter * torch.randn(x.shape, generator=randkey.generator(x.device),
                                                device=x.device, dtype=x.dtype)
         return self._sumstats(params, x)
+
+
+@dataclass(eq=False)
+class BinnedPopulationSMFModel(TorchPopulationSMFModel):
+    """The same model and loss with the binning done by
+    :func:`~multigrad_amd.ops.binned.gaussian_binned_sum`: what a user writes -- the gather
+    and the parameter transforms in torch, the Gaussian-smeared histogram in the fused op.
+    The bin edges are kept as a host tuple at construction (the op takes host edges, so a
+    captured step never reads them back from the device)."""
+
+    def __post_init__(self):
+        super().__post_init__()
+        self.edges = tuple(float(e) for e in self.aux_data["edges"].tolist())
+
+    def _sumstats(self, params, x):
+        d = self.aux_data
+        th = params.reshape(-1, 2)
+        a = th[:, 0][d["pop"]]
+        sigma = torch.pow(10.0, th[:, 1])[d["pop"]]
+        return gaussian_binned_sum(x + a, sigma, self.edges, None) * d["scale"]
