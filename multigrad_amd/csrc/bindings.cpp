@@ -130,6 +130,13 @@ torch::Tensor binned_forward(torch::Tensor mu, torch::Tensor sigma, c10::optiona
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> binned_backward(
     torch::Tensor mu, torch::Tensor sigma, c10::optional<torch::Tensor> w, std::vector<double> edges,
     torch::Tensor g, bool need_mu, bool need_sigma, bool need_w);
+// groups.hip
+int64_t group_chunk();
+std::vector<torch::Tensor> group_gather(torch::Tensor ids, std::vector<torch::Tensor> values,
+                                        int64_t num_groups);
+std::vector<torch::Tensor> group_segment_sum(torch::Tensor sorted_ids,
+                                             c10::optional<torch::Tensor> perm,
+                                             std::vector<torch::Tensor> x, int64_t num_groups);
 // runtime.cpp
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int64_t>
 build_tiles(torch::Tensor counts, std::vector<int64_t> breaks, int64_t tile_halos,
@@ -229,6 +236,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("compact_diag", &mg::compact_diag);
   m.def("binned_forward", &mg::binned_forward);
   m.def("binned_backward", &mg::binned_backward);
+  m.def("group_chunk", &mg::group_chunk);
+  m.def("group_gather", &mg::group_gather);
+  m.def("group_segment_sum", &mg::group_segment_sum);
   m.def("build_tiles", &mg::build_tiles);
   m.def("sort_by_population", &mg::sort_by_population);
   m.def("build_lanes", &mg::build_lanes, pybind11::arg("counts"), pybind11::arg("breaks"),

@@ -15,11 +15,13 @@ from dataclasses import dataclass
 import torch
 
 from ..ops.binned import gaussian_binned_sum
+from ..ops.groups import GroupIndex
 from ..ops.smf import logmse_loss
 from .onepoint import OnePointModel
 
 __all__ = ["TorchPopulationSMFModel", "StochasticTorchPopulationSMFModel",
-           "BinnedPopulationSMFModel", "torch_population_data"]
+           "BinnedPopulationSMFModel", "GroupedBinnedPopulationSMFModel",
+           "torch_population_data"]
 
 
 def torch_population_data(data: dict) -> dict:
@@ -94,4 +96,22 @@ class BinnedPopulationSMFModel(TorchPopulationSMFModel):
         th = params.reshape(-1, 2)
         a = th[:, 0][d["pop"]]
         sigma = torch.pow(10.0, th[:, 1])[d["pop"]]
+        return gaussian_binned_sum(x + a, sigma, self.edges, None) * d["scale"]
+
+
+@dataclass(eq=False)
+class GroupedBinnedPopulationSMFModel(BinnedPopulationSMFModel):
+    """:class:`BinnedPopulationSMFModel` with the two gathers done by a
+    :class:`~multigrad_amd.ops.groups.GroupIndex` built once from the population ids: the
+    backward of ``a[pop]`` and ``sigma[pop]`` is then one fixed-order segmented sum of both
+    gradient columns instead of a sort and an atomic scatter per step."""
+
+    def __post_init__(self):
+        super().__post_init__()
+        self.groups = GroupIndex(self.aux_data["pop"], self.aux_data["npop"])
+
+    def _sumstats(self, params, x):
+        d = self.aux_data
+        th = params.reshape(-1, 2)
+        a, sigma = self.groups.gather(th[:, 0], torch.pow(10.0, th[:, 1]))
         return gaussian_binned_sum(x + a, sigma, self.edges, None) * d["scale"]

@@ -1,11 +1,14 @@
 """Device ops: hand-written gfx950 HIP kernels (``csrc/``) behind thin Python wrappers."""
 from ._ext import available, ext
 
-__all__ = ["available", "ext", "gaussian_binned_sum"]
+__all__ = ["available", "ext", "gaussian_binned_sum", "GroupIndex", "group_gather", "segment_sum"]
 
 
 def __getattr__(name):  # lazy: importing the package loads no op module and no device
     if name == "gaussian_binned_sum":
         from .binned import gaussian_binned_sum
         return gaussian_binned_sum
+    if name in ("GroupIndex", "group_gather", "segment_sum"):
+        from . import groups
+        return getattr(groups, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
