@@ -56,12 +56,12 @@ once and there is nothing to overlap inside the VJP.
 from __future__ import annotations
 
 import math
-import os
 import weakref
 from typing import Optional
 
 import torch
 
+from ._env import env_flag, env_int
 from ._stream import EngineStream, make_engine_stream, on_engine_stream
 from ..ops.adam import adam_step_
 from ..optim.adam import History
@@ -136,11 +136,6 @@ def _leaf_view(p: torch.Tensor, shape) -> torch.Tensor:
     return p.detach().view(shape).requires_grad_(True)
 
 
-def _step_replay_default() -> bool:
-    """``MULTIGRAD_STEP_REPLAY``: whether direct ``step()`` calls may replay graphs."""
-    return os.environ.get("MULTIGRAD_STEP_REPLAY", "0").strip().lower() in ("1", "on", "true", "yes")
-
-
 class GraphAdamEngine:
     """Adam over a generic :class:`~multigrad_amd.models.onepoint.OnePointModel` (or a
     :class:`~multigrad_amd.models.onepoint.OnePointGroup` of them).
@@ -157,17 +152,16 @@ class GraphAdamEngine:
         self.comm = default if comm is None else comm
         self.size = 1 if self.comm is None else self.comm.size
         self.rank = 0 if self.comm is None else self.comm.rank
-        env = os.environ.get("MULTIGRAD_GRAPH")
-        if graph is None and env is not None:
-            graph = env.lower() not in ("0", "false", "off", "no")
+        if graph is None:
+            graph = env_flag("MULTIGRAD_GRAPH")
         self.graph_req = graph
         self.graph = None
         self._kgraph = None
-        self.graph_steps = max(1, int(os.environ.get("MULTIGRAD_GRAPH_STEPS", "16")))
+        self.graph_steps = max(1, env_int("MULTIGRAD_GRAPH_STEPS", 16))
         # direct step() calls replay graphs only when the caller promises to launch nothing
         # on the legacy default stream between them (engine/_stream.py); the engine's own
         # drivers (steps(), run_adam, run_simple_grad_descent) always may
-        self.step_replay = _step_replay_default()
+        self.step_replay = env_flag("MULTIGRAD_STEP_REPLAY", False)
         self.use_graph = False
         self.fallback_reason = None
         self.oneshot = None          # main-communicator one-shot (group loss)
@@ -356,7 +350,7 @@ class GraphAdamEngine:
             self.lg = torch.zeros(1 + P, **f32)
         self.graph = None
         self._kgraph = None
-        self.graph_steps = max(1, int(os.environ.get("MULTIGRAD_GRAPH_STEPS", "16")))
+        self.graph_steps = max(1, env_int("MULTIGRAD_GRAPH_STEPS", 16))
         self.tuning = None
         self._times = {}
         self.fallback_reason = None

@@ -28,11 +28,11 @@ captures), the analogue of JAX's jit cache the reference relies on
 from __future__ import annotations
 
 import math
-import os
 from typing import Optional
 
 import torch
 
+from ._env import env_choice, env_flag, env_int
 from ._stream import EngineStream, make_engine_stream, on_engine_stream
 
 __all__ = ["Smf2Engine", "smf2_eligible"]
@@ -46,7 +46,7 @@ def _ext():
 def smf2_eligible(model) -> bool:
     """Whether ``model`` (an SMF model of :mod:`multigrad_amd.models.smf`) can run on the
     fused step: on a GPU, absolute tails, at most 16 (padded) bins, fp32 shard."""
-    if os.environ.get("MULTIGRAD_SMF2", "1").lower() in ("0", "off", "false", "no"):
+    if not env_flag("MULTIGRAD_SMF2", True):
         return False
     if getattr(model, "dtype", None) not in (None, torch.float32):
         return False   # an fp64 model keeps the PyTorch path
@@ -93,21 +93,21 @@ class Smf2Engine:
             from ..parallel.xgmi import get_oneshot
             self.oneshot = get_oneshot(self.comm)  # collective
         self.nmax = nmax
-        lm = int(os.environ.get("MULTIGRAD_SMF2_LOOP_MAX", str(1 << 16)))
-        sched = os.environ.get("MULTIGRAD_SMF2_SCHEDULE", "auto").lower()
+        lm = env_int("MULTIGRAD_SMF2_LOOP_MAX", 1 << 16)
+        sched = env_choice("MULTIGRAD_SMF2_SCHEDULE", "auto", ("auto", "loop", "grid"))
         # the persistent loop carries its exchange inside the launch: it needs the peer
         # exchange on several ranks
         loop_ok = self.size == 1 or self.oneshot is not None
         self.schedule = ("loop" if (sched == "loop" or (sched == "auto" and nmax <= lm))
                          and loop_ok else "grid")
-        self.loop_steps = max(1, int(os.environ.get("MULTIGRAD_SMF2_LOOP_STEPS", "1000")))
-        self.graph_steps = max(1, int(os.environ.get("MULTIGRAD_SMF2_GRAPH_STEPS", "16")))
-        self.use_graph = (os.environ.get("MULTIGRAD_GRAPH", "1") != "0"
+        self.loop_steps = max(1, env_int("MULTIGRAD_SMF2_LOOP_STEPS", 1000))
+        self.graph_steps = max(1, env_int("MULTIGRAD_SMF2_GRAPH_STEPS", 16))
+        self.use_graph = (env_flag("MULTIGRAD_GRAPH", True)
                           and (self.size == 1 or self.oneshot is not None))
         blocks = int(_ext().smf2_fwd_max_blocks(bins.nb, self.log_sigma))
         # at least MULTIGRAD_SMF2_HALOS_PER_THREAD halos per thread: fewer slab rows for the
         # one-workgroup step kernel to sum when the shard is small
-        hpt = max(1, int(os.environ.get("MULTIGRAD_SMF2_HALOS_PER_THREAD", "16")))
+        hpt = max(1, env_int("MULTIGRAD_SMF2_HALOS_PER_THREAD", 16))
         self.nblocks = max(1, min(blocks, -(-max(self.n, 1) // (256 * hpt)), 65535))
         f32 = dict(dtype=torch.float32, device=self.device)
         self.slab = torch.zeros(self.nblocks * self.R, **f32)

@@ -201,7 +201,7 @@ def make_population_data(num_params: int = 10_000_000, num_halos: int = 1 << 27,
     populations take the per-edge path (profiles/narrow_sweep/).  ``narrow_guess_log_sigma``:
     the starting log10 sigma of those populations (default: truth + offset, as the others);
     a wide start (e.g. -0.6, inside the Euler-Maclaurin range) makes a fit move them across
-    the limit while it runs (the engine's re-layout, engine/fused.py).
+    the limit while it runs (the engine's re-layout, engine/_relayout.py).
 
     Returns a dict with the sorted device shard (``shard``), bins, volume, true
     parameters ``truth`` (interleaved, device) and a starting ``guess``; the target SMF is
