@@ -130,6 +130,15 @@ torch::Tensor binned_forward(torch::Tensor mu, torch::Tensor sigma, c10::optiona
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> binned_backward(
     torch::Tensor mu, torch::Tensor sigma, c10::optional<torch::Tensor> w, std::vector<double> edges,
     torch::Tensor g, bool need_mu, bool need_sigma, bool need_w);
+// binned2d.hip
+torch::Tensor binned2d_forward(torch::Tensor mux, torch::Tensor sigx, torch::Tensor muy,
+                               torch::Tensor sigy, c10::optional<torch::Tensor> w,
+                               std::vector<double> ex, std::vector<double> ey);
+std::vector<torch::Tensor> binned2d_backward(torch::Tensor mux, torch::Tensor sigx,
+                                             torch::Tensor muy, torch::Tensor sigy,
+                                             c10::optional<torch::Tensor> w, std::vector<double> ex,
+                                             std::vector<double> ey, torch::Tensor g,
+                                             std::vector<bool> need);
 // groups.hip
 int64_t group_chunk();
 std::vector<torch::Tensor> group_gather(torch::Tensor ids, std::vector<torch::Tensor> values,
@@ -236,6 +245,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("compact_diag", &mg::compact_diag);
   m.def("binned_forward", &mg::binned_forward);
   m.def("binned_backward", &mg::binned_backward);
+  m.def("binned2d_forward", &mg::binned2d_forward);
+  m.def("binned2d_backward", &mg::binned2d_backward);
   m.def("group_chunk", &mg::group_chunk);
   m.def("group_gather", &mg::group_gather);
   m.def("group_segment_sum", &mg::group_segment_sum);

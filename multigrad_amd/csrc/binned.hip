@@ -18,15 +18,12 @@
 #include <tuple>
 #include <vector>
 
-#include "common.h"
+#include "binned_common.h"
 #include "smf_host.h"
 
 namespace mg {
 
 namespace {
-
-constexpr int kBinThreads = 256;
-constexpr float kInvSqrt2PiB = 0x1.988454p-2f;  // 1/sqrt(2 pi)
 
 struct BinnedArgs {
   const float* mu;
@@ -56,22 +53,12 @@ __device__ __forceinline__ void load_quad(const BinnedArgs& a, int64_t q, float 
   const int64_t i0 = q * 4;
   float s[4];
   if (a.vec && i0 + 4 <= a.n) {
-    const float4 mv = *reinterpret_cast<const float4*>(a.mu + i0);
-    m[0] = mv.x; m[1] = mv.y; m[2] = mv.z; m[3] = mv.w;
-    if (a.sig_b) {
-      s[0] = s[1] = s[2] = s[3] = a.sigma[0];
-    } else {
-      const float4 sv = *reinterpret_cast<const float4*>(a.sigma + i0);
-      s[0] = sv.x; s[1] = sv.y; s[2] = sv.z; s[3] = sv.w;
-    }
-    if (a.w == nullptr) {
-      wt[0] = wt[1] = wt[2] = wt[3] = 1.0f;
-    } else if (a.w_b) {
-      wt[0] = wt[1] = wt[2] = wt[3] = a.w[0];
-    } else {
-      const float4 wv = *reinterpret_cast<const float4*>(a.w + i0);
-      wt[0] = wv.x; wt[1] = wv.y; wt[2] = wv.z; wt[3] = wv.w;
-    }
+    wide_load<4>(a.mu, i0, m);
+    if (a.sig_b) splat(a.sigma[0], s);
+    else wide_load<4>(a.sigma, i0, s);
+    if (a.w == nullptr) splat(1.0f, wt);
+    else if (a.w_b) splat(a.w[0], wt);
+    else wide_load<4>(a.w, i0, wt);
   } else {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -84,17 +71,6 @@ __device__ __forceinline__ void load_quad(const BinnedArgs& a, int64_t q, float 
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j) inv[j] = 1.0f / s[j];
-}
-
-// Phi(z) = base + frac with base in {0, 1} and |frac| = Q(|z|) <= 1/2: the difference of two
-// edges on the same side of the mean is then formed from the small parts alone.  ws = z*kWScale.
-__device__ __forceinline__ void edge_cdf(float z, float& base, float& frac, float& gauss) {
-  float p;
-  normal_tail_parts_w<false>(z * kWScale, p, gauss);
-  const float q = p * gauss;
-  const bool up = z >= 0.0f;
-  base = up ? 1.0f : 0.0f;
-  frac = up ? -q : q;
 }
 
 template <int NB>
@@ -139,36 +115,16 @@ __global__ __launch_bounds__(kBinThreads) void binned_fwd_kernel(BinnedArgs a, f
   }
 }
 
-// Fixed-order sum of slab rows [rows, ncols] (ncols a power of two <= 32) by one workgroup:
-// thread t owns column t % ncols and the rows t / ncols, + groups, ... (four independent
-// partial sums, so four loads are in flight); the groups are then folded by a tree in LDS.
-// The order depends only on (rows, ncols).  Columns [0, na) go to out_a, column na to out_b
-// (either may be null: the column is dropped).
-constexpr int kRedThreads = 1024;
-
+// Fixed-order sum of slab rows [rows, ncols] (ncols a power of two <= 32) by one workgroup
+// (slab_column_sum).  Columns [0, na) go to out_a, column na to out_b (either may be null:
+// the column is dropped).
 __global__ __launch_bounds__(kRedThreads) void binned_reduce_kernel(const float* slab, int64_t rows,
                                                                     int ncols, float* out_a, int na,
                                                                     float* out_b) {
   __shared__ float part[kRedThreads];
-  const int k = threadIdx.x % ncols;
-  const int64_t groups = kRedThreads / ncols;
-  float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-  int64_t r = threadIdx.x / ncols;
-  for (; r + 3 * groups < rows; r += 4 * groups) {
-    s0 += slab[r * ncols + k];
-    s1 += slab[(r + groups) * ncols + k];
-    s2 += slab[(r + 2 * groups) * ncols + k];
-    s3 += slab[(r + 3 * groups) * ncols + k];
-  }
-  for (; r < rows; r += groups) s0 += slab[r * ncols + k];
-  part[threadIdx.x] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  for (int half = kRedThreads / 2; half >= ncols; half >>= 1) {
-    if ((int)threadIdx.x < half) part[threadIdx.x] += part[threadIdx.x + half];
-    __syncthreads();
-  }
-  if ((int)threadIdx.x < ncols) {
-    const float t = part[threadIdx.x];
+  float t;
+  if (slab_column_sum(slab, rows, ncols, 0, ncols, part, t)) {
+    const int k = threadIdx.x;
     if (k < na) {
       if (out_a) out_a[k] = t;
     } else if (k == na && out_b) {
@@ -291,7 +247,7 @@ int binned_padded(int nb) {
     default: { constexpr int NB = 32; __VA_ARGS__; break; } \
   }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+bool aligned16(const void* p) { return aligned_to(p, 16); }
 
 // Workgroups that fill the chip once (occupancy x CU count of the device), per kernel.
 template <auto Kernel>

@@ -1,0 +1,121 @@
+// Device helpers shared by the Gaussian-binned-sum ops (binned.hip, binned2d.hip): the edge
+// CDF, guarded vector loads of per-object operands and the fixed-order slab column sum.
+#pragma once
+#include "common.h"
+
+namespace mg {
+
+constexpr int kBinThreads = 256;
+constexpr int kRedThreads = 1024;
+constexpr float kInvSqrt2PiB = 0x1.988454p-2f;  // 1/sqrt(2 pi)
+
+inline bool aligned_to(const void* p, uintptr_t bytes) {
+  return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0;
+}
+
+// Phi(z) = base + frac with base in {0, 1} and |frac| = Q(|z|) <= 1/2: the difference of two
+// edges on the same side of the mean is then formed from the small parts alone.  ws = z*kWScale.
+__device__ __forceinline__ void edge_cdf(float z, float& base, float& frac, float& gauss) {
+  float p;
+  normal_tail_parts_w<false>(z * kWScale, p, gauss);
+  const float q = p * gauss;
+  const bool up = z >= 0.0f;
+  base = up ? 1.0f : 0.0f;
+  frac = up ? -q : q;
+}
+
+// V (2 or 4) consecutive elements p[i0 .. i0+V) of a per-object operand, read in groups: a
+// full group of an aligned operand takes one 4*V-byte load (wide_load); a misaligned view
+// and the last n % V elements take guarded scalar loads (guarded_load, never past the end;
+// an element beyond n gives `fill`, a broadcast operand reads p[0]).
+template <int V>
+__device__ __forceinline__ void wide_load(const float* p, int64_t i0, float (&v)[V]) {
+  static_assert(V == 2 || V == 4, "wide_load: 8- or 16-byte groups");
+  if constexpr (V == 4) {
+    const float4 t = *reinterpret_cast<const float4*>(p + i0);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+    const float2 t = *reinterpret_cast<const float2*>(p + i0);
+    v[0] = t.x; v[1] = t.y;
+  }
+}
+
+template <int V>
+__device__ __forceinline__ void guarded_load(const float* p, int64_t i0, int64_t n, bool bcast,
+                                             float fill, float (&v)[V]) {
+#pragma unroll
+  for (int j = 0; j < V; ++j) v[j] = i0 + j < n ? p[bcast ? 0 : i0 + j] : fill;
+}
+
+template <int V>
+__device__ __forceinline__ void splat(float x, float (&v)[V]) {
+#pragma unroll
+  for (int j = 0; j < V; ++j) v[j] = x;
+}
+
+// One operand of a group: `full` is "the group is whole and every operand is aligned"
+// (the caller's single branch); a null pointer stands for the constant `fill_null`.
+template <int V>
+__device__ __forceinline__ void load_group(const float* p, int64_t i0, int64_t n, bool full,
+                                           bool bcast, float fill_null, float fill_end,
+                                           float (&v)[V]) {
+  if (full) {
+    if (p == nullptr) splat(fill_null, v);
+    else if (bcast) splat(p[0], v);
+    else wide_load<V>(p, i0, v);
+  } else if (p == nullptr) {
+#pragma unroll
+    for (int j = 0; j < V; ++j) v[j] = i0 + j < n ? fill_null : fill_end;
+  } else {
+    guarded_load<V>(p, i0, n, bcast, fill_end, v);
+  }
+}
+
+// V consecutive results to p[i0 .. i0+V): one 4*V-byte store for a full group (p is a fresh
+// allocation, hence aligned), guarded scalar stores for the last n % V elements.
+template <int V>
+__device__ __forceinline__ void store_group(float* p, int64_t i0, int64_t n, const float (&v)[V]) {
+  static_assert(V == 2 || V == 4, "store_group: 8- or 16-byte groups");
+  if (i0 + V <= n) {
+    if constexpr (V == 4)
+      *reinterpret_cast<float4*>(p + i0) = make_float4(v[0], v[1], v[2], v[3]);
+    else
+      *reinterpret_cast<float2*>(p + i0) = make_float2(v[0], v[1]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < V; ++j)
+      if (i0 + j < n) p[i0 + j] = v[j];
+  }
+}
+
+// Fixed-order sum of `ncols` columns (a power of two <= 32) starting at column col0 of the
+// slab rows [rows, ld], by one workgroup of kRedThreads threads: thread t owns column
+// t % ncols and the rows t / ncols, + groups, ... (four independent partial sums, so four
+// loads are in flight); the groups are then folded by a tree in LDS (part: kRedThreads
+// floats).  The order depends only on (rows, ncols).  Threads [0, ncols) return true with the
+// total of column col0 + threadIdx.x.
+__device__ __forceinline__ bool slab_column_sum(const float* slab, int64_t rows, int64_t ld,
+                                                int col0, int ncols, float* part, float& total) {
+  const int k = threadIdx.x % ncols;
+  const int64_t groups = kRedThreads / ncols;
+  const float* col = slab + col0 + k;
+  float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+  int64_t r = threadIdx.x / ncols;
+  for (; r + 3 * groups < rows; r += 4 * groups) {
+    s0 += col[r * ld];
+    s1 += col[(r + groups) * ld];
+    s2 += col[(r + 2 * groups) * ld];
+    s3 += col[(r + 3 * groups) * ld];
+  }
+  for (; r < rows; r += groups) s0 += col[r * ld];
+  part[threadIdx.x] = (s0 + s1) + (s2 + s3);
+  __syncthreads();
+  for (int half = kRedThreads / 2; half >= ncols; half >>= 1) {
+    if ((int)threadIdx.x < half) part[threadIdx.x] += part[threadIdx.x + half];
+    __syncthreads();
+  }
+  total = part[threadIdx.x];
+  return (int)threadIdx.x < ncols;
+}
+
+}  // namespace mg

@@ -15,13 +15,14 @@ from dataclasses import dataclass
 import torch
 
 from ..ops.binned import gaussian_binned_sum
+from ..ops.binned2d import gaussian_binned_sum_2d
 from ..ops.groups import GroupIndex
 from ..ops.smf import logmse_loss
 from .onepoint import OnePointModel
 
 __all__ = ["TorchPopulationSMFModel", "StochasticTorchPopulationSMFModel",
            "BinnedPopulationSMFModel", "GroupedBinnedPopulationSMFModel",
-           "torch_population_data"]
+           "JointBinnedPopulationSMFModel", "torch_population_data", "joint_population_data"]
 
 
 def torch_population_data(data: dict) -> dict:
@@ -115,3 +116,63 @@ class GroupedBinnedPopulationSMFModel(BinnedPopulationSMFModel):
         th = params.reshape(-1, 2)
         a, sigma = self.groups.gather(th[:, 0], torch.pow(10.0, th[:, 1]))
         return gaussian_binned_sum(x + a, sigma, self.edges, None) * d["scale"]
+
+
+@dataclass(eq=False)
+class JointBinnedPopulationSMFModel(GroupedBinnedPopulationSMFModel):
+    """A joint statistic on :func:`~multigrad_amd.ops.binned2d.gaussian_binned_sum_2d`: counts
+    in (log stellar mass x a second observable ``y``), both axes smeared by the population's
+    parameters -- ``mu_x = x + a``, ``sigma_x = sigma``, ``mu_y = y + y_slope * a``,
+    ``sigma_y = y_width * sigma`` -- so all four per-object gradients flow.  ``aux_data`` from
+    :func:`joint_population_data`: the per-halo ``y``, the host ``edges_y`` and ``scale`` /
+    ``target`` of ``nbx * nby`` flattened cells.  With the default ``y_width`` the y smearing
+    stays well inside a y bin, so widening a population never spills more out of the grid
+    in y than it gains in x and every population's sigma gradient keeps one sign (at 1.5 a
+    few change sign, and gradient elements that are near-cancellations cannot be compared
+    between float32 implementations)."""
+
+    y_slope: float = 0.5
+    y_width: float = 0.5
+
+    def __post_init__(self):
+        super().__post_init__()
+        self.edges_y = tuple(float(e) for e in self.aux_data["edges_y"])
+
+    def _cells(self, mu_x, sigma_x, mu_y, sigma_y):
+        return gaussian_binned_sum_2d(mu_x, sigma_x, mu_y, sigma_y, self.edges, self.edges_y)
+
+    def _sumstats(self, params, x):
+        d = self.aux_data
+        th = params.reshape(-1, 2)
+        a, sigma = self.groups.gather(th[:, 0], torch.pow(10.0, th[:, 1]))
+        cells = self._cells(x + a, sigma, d["y"] + self.y_slope * a, self.y_width * sigma)
+        return cells.reshape(-1) * d["scale"]
+
+
+def joint_population_data(data: dict, nby: int = 4, y_range=(-12.0, -10.0), seed: int = 0,
+                          **model_kwargs) -> dict:
+    """``aux_data`` of :class:`JointBinnedPopulationSMFModel` from
+    :func:`~multigrad_amd.models.population.make_population_data` output: the second
+    coordinate ``y`` is drawn independently of ``x`` so that ``mu_y`` at the mean true offset
+    is uniform across ``nby`` equal bins of ``y_range`` (a small ``nby`` keeps every cell
+    populated), the per-bin scale is repeated
+    over the y bins, and the target is the model's own sumstats at ``data["truth"]``."""
+    sh = data["shard"]
+    bins = data["bins"]
+    dev = sh.x.device
+    n = sh.x.numel()
+    gen = torch.Generator().manual_seed(1000 + seed)
+    slope = float(model_kwargs.get("y_slope", JointBinnedPopulationSMFModel.y_slope))
+    shift = slope * float(data["truth"].reshape(-1, 2)[:, 0].float().mean())
+    y = (y_range[0] - shift + (y_range[1] - y_range[0]) * torch.rand(n, generator=gen)).to(dev)
+    edges_y = tuple(float(y_range[0] + (y_range[1] - y_range[0]) * k / nby) for k in range(nby + 1))
+    scale = torch.tensor(bins.scale, dtype=torch.float32, device=dev).repeat_interleave(nby)
+    aux = dict(x=sh.x.float(), pop=sh.pop.long(), y=y,
+               edges=torch.tensor(bins.edges, dtype=torch.float32, device=dev), edges_y=edges_y,
+               scale=scale, target=torch.ones_like(scale), eps=float(data["loss_eps"]),
+               npop=int(data["npop"]))
+    model = JointBinnedPopulationSMFModel(aux_data=aux, **model_kwargs)
+    with torch.no_grad():
+        aux["target"] = model.calc_sumstats_from_params(
+            data["truth"].to(dev, torch.float32)).float()
+    return aux

@@ -1,13 +1,17 @@
 """Device ops: hand-written gfx950 HIP kernels (``csrc/``) behind thin Python wrappers."""
 from ._ext import available, ext
 
-__all__ = ["available", "ext", "gaussian_binned_sum", "GroupIndex", "group_gather", "segment_sum"]
+__all__ = ["available", "ext", "gaussian_binned_sum", "gaussian_binned_sum_2d",
+           "GroupIndex", "group_gather", "segment_sum"]
 
 
 def __getattr__(name):  # lazy: importing the package loads no op module and no device
     if name == "gaussian_binned_sum":
         from .binned import gaussian_binned_sum
         return gaussian_binned_sum
+    if name == "gaussian_binned_sum_2d":
+        from .binned2d import gaussian_binned_sum_2d
+        return gaussian_binned_sum_2d
     if name in ("GroupIndex", "group_gather", "segment_sum"):
         from . import groups
         return getattr(groups, name)
