@@ -139,6 +139,15 @@ std::vector<torch::Tensor> binned2d_backward(torch::Tensor mux, torch::Tensor si
                                              c10::optional<torch::Tensor> w, std::vector<double> ex,
                                              std::vector<double> ey, torch::Tensor g,
                                              std::vector<bool> need);
+// binned_multi.hip
+torch::Tensor binned_multi_forward(torch::Tensor mu, torch::Tensor sigma,
+                                   std::vector<c10::optional<torch::Tensor>> weights,
+                                   std::vector<double> edges);
+std::vector<torch::Tensor> binned_multi_backward(torch::Tensor mu, torch::Tensor sigma,
+                                                 std::vector<c10::optional<torch::Tensor>> weights,
+                                                 std::vector<double> edges, torch::Tensor g,
+                                                 bool need_mu, bool need_sigma,
+                                                 std::vector<bool> need_w);
 // groups.hip
 int64_t group_chunk();
 std::vector<torch::Tensor> group_gather(torch::Tensor ids, std::vector<torch::Tensor> values,
@@ -247,6 +256,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("binned_backward", &mg::binned_backward);
   m.def("binned2d_forward", &mg::binned2d_forward);
   m.def("binned2d_backward", &mg::binned2d_backward);
+  m.def("binned_multi_forward", &mg::binned_multi_forward);
+  m.def("binned_multi_backward", &mg::binned_multi_backward);
   m.def("group_chunk", &mg::group_chunk);
   m.def("group_gather", &mg::group_gather);
   m.def("group_segment_sum", &mg::group_segment_sum);

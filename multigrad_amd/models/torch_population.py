@@ -16,13 +16,15 @@ import torch
 
 from ..ops.binned import gaussian_binned_sum
 from ..ops.binned2d import gaussian_binned_sum_2d
+from ..ops.binned_multi import gaussian_binned_sum_multi
 from ..ops.groups import GroupIndex
 from ..ops.smf import logmse_loss
 from .onepoint import OnePointModel
 
 __all__ = ["TorchPopulationSMFModel", "StochasticTorchPopulationSMFModel",
            "BinnedPopulationSMFModel", "GroupedBinnedPopulationSMFModel",
-           "JointBinnedPopulationSMFModel", "torch_population_data", "joint_population_data"]
+           "JointBinnedPopulationSMFModel", "ConditionalBinnedPopulationSMFModel",
+           "torch_population_data", "joint_population_data", "conditional_population_data"]
 
 
 def torch_population_data(data: dict) -> dict:
@@ -172,6 +174,55 @@ def joint_population_data(data: dict, nby: int = 4, y_range=(-12.0, -10.0), seed
                scale=scale, target=torch.ones_like(scale), eps=float(data["loss_eps"]),
                npop=int(data["npop"]))
     model = JointBinnedPopulationSMFModel(aux_data=aux, **model_kwargs)
+    with torch.no_grad():
+        aux["target"] = model.calc_sumstats_from_params(
+            data["truth"].to(dev, torch.float32)).float()
+    return aux
+
+
+@dataclass(eq=False)
+class ConditionalBinnedPopulationSMFModel(GroupedBinnedPopulationSMFModel):
+    """Three statistics over the same stellar-mass bins on
+    :func:`~multigrad_amd.ops.binned_multi.gaussian_binned_sum_multi`, ``3 * nb`` sumstats:
+    the counts (weight ``None``), a quenched-weighted count with
+    ``q_i = sigmoid(q_slope * (x_i + a_i - q_mass))`` -- a weight that depends on the
+    parameters, so its gradient flows through the op's weight gradient -- and the sum of a
+    fixed per-halo observable ``y_i`` in ``[0.5, 1.5]`` (a weight that needs no gradient).
+    ``aux_data`` from :func:`conditional_population_data`: the per-halo ``y`` and ``scale`` /
+    ``target`` of ``3 * nb`` entries (the per-bin scale repeated per statistic).  All three
+    weights are positive, so every sumstat is positive and the log-MSE loss applies."""
+
+    q_slope: float = 2.0
+    q_mass: float = 10.0
+
+    def _sums(self, mu, sigma, weights):
+        return gaussian_binned_sum_multi(mu, sigma, self.edges, weights)
+
+    def _sumstats(self, params, x):
+        d = self.aux_data
+        th = params.reshape(-1, 2)
+        a, sigma = self.groups.gather(th[:, 0], torch.pow(10.0, th[:, 1]))
+        mu = x + a
+        q = torch.sigmoid(self.q_slope * (mu - self.q_mass))
+        return self._sums(mu, sigma, (None, q, d["y"])).reshape(-1) * d["scale"]
+
+
+def conditional_population_data(data: dict, seed: int = 0, **model_kwargs) -> dict:
+    """``aux_data`` of :class:`ConditionalBinnedPopulationSMFModel` from
+    :func:`~multigrad_amd.models.population.make_population_data` output: the per-halo
+    observable ``y`` is uniform in ``[0.5, 1.5]``, the per-bin scale is repeated for the three
+    statistics, and the target is the model's own sumstats at ``data["truth"]``."""
+    sh = data["shard"]
+    bins = data["bins"]
+    dev = sh.x.device
+    gen = torch.Generator().manual_seed(2000 + seed)
+    y = (0.5 + torch.rand(sh.x.numel(), generator=gen)).to(dev)
+    scale = torch.tensor(bins.scale, dtype=torch.float32, device=dev).repeat(3)
+    aux = dict(x=sh.x.float(), pop=sh.pop.long(), y=y,
+               edges=torch.tensor(bins.edges, dtype=torch.float32, device=dev),
+               scale=scale, target=torch.ones_like(scale), eps=float(data["loss_eps"]),
+               npop=int(data["npop"]))
+    model = ConditionalBinnedPopulationSMFModel(aux_data=aux, **model_kwargs)
     with torch.no_grad():
         aux["target"] = model.calc_sumstats_from_params(
             data["truth"].to(dev, torch.float32)).float()
