@@ -130,6 +130,11 @@ torch::Tensor binned_forward(torch::Tensor mu, torch::Tensor sigma, c10::optiona
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> binned_backward(
     torch::Tensor mu, torch::Tensor sigma, c10::optional<torch::Tensor> w, std::vector<double> edges,
     torch::Tensor g, bool need_mu, bool need_sigma, bool need_w);
+// binned_hvp.hip
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> binned_backward2(
+    torch::Tensor mu, torch::Tensor sigma, c10::optional<torch::Tensor> w, std::vector<double> edges,
+    torch::Tensor g, c10::optional<torch::Tensor> ca, c10::optional<torch::Tensor> cb,
+    c10::optional<torch::Tensor> cc, bool need_mu, bool need_sigma, bool need_w, bool need_g);
 // binned2d.hip
 torch::Tensor binned2d_forward(torch::Tensor mux, torch::Tensor sigx, torch::Tensor muy,
                                torch::Tensor sigy, c10::optional<torch::Tensor> w,
@@ -254,6 +259,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("compact_diag", &mg::compact_diag);
   m.def("binned_forward", &mg::binned_forward);
   m.def("binned_backward", &mg::binned_backward);
+  m.def("binned_backward2", &mg::binned_backward2);
   m.def("binned2d_forward", &mg::binned2d_forward);
   m.def("binned2d_backward", &mg::binned2d_backward);
   m.def("binned_multi_forward", &mg::binned_multi_forward);

@@ -18,24 +18,11 @@
 #include <tuple>
 #include <vector>
 
-#include "binned_common.h"
-#include "smf_host.h"
+#include "binned_host.h"
 
 namespace mg {
 
 namespace {
-
-struct BinnedArgs {
-  const float* mu;
-  const float* sigma;
-  const float* w;  // nullptr: every weight is 1
-  int64_t n;
-  int nb;     // real bins (<= the padded template count)
-  int sig_b;  // sigma has one element
-  int w_b;    // w has one element
-  int vec;    // every input pointer is 16-byte aligned
-  float edge[kMaxBins + 1];
-};
 
 struct BinnedGrad {
   const float* g;  // [nb] cotangent
@@ -44,34 +31,6 @@ struct BinnedGrad {
   float* dw;       // [n], or [1] when w is broadcast
   float* slab;     // [blocks, 2] partial sums of the broadcast gradients (col 0 sigma, col 1 w)
 };
-
-// Four consecutive objects of quad q: mean, 1/sigma and weight.  A full quad of aligned
-// inputs is read with one 16-byte load per operand; a misaligned view and the last N % 4
-// objects take guarded scalar loads (never past the end).  Objects beyond N get weight 0.
-__device__ __forceinline__ void load_quad(const BinnedArgs& a, int64_t q, float (&m)[4],
-                                          float (&inv)[4], float (&wt)[4]) {
-  const int64_t i0 = q * 4;
-  float s[4];
-  if (a.vec && i0 + 4 <= a.n) {
-    wide_load<4>(a.mu, i0, m);
-    if (a.sig_b) splat(a.sigma[0], s);
-    else wide_load<4>(a.sigma, i0, s);
-    if (a.w == nullptr) splat(1.0f, wt);
-    else if (a.w_b) splat(a.w[0], wt);
-    else wide_load<4>(a.w, i0, wt);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int64_t i = i0 + j;
-      const bool ok = i < a.n;
-      m[j] = ok ? a.mu[i] : 0.0f;
-      s[j] = ok ? a.sigma[a.sig_b ? 0 : i] : 1.0f;
-      wt[j] = !ok ? 0.0f : a.w == nullptr ? 1.0f : a.w[a.w_b ? 0 : i];
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) inv[j] = 1.0f / s[j];
-}
 
 template <int NB>
 __global__ __launch_bounds__(kBinThreads) void binned_fwd_kernel(BinnedArgs a, float* slab,
@@ -234,28 +193,6 @@ __global__ __launch_bounds__(kBinThreads) void binned_bwd_kernel(BinnedArgs a, B
   }
 }
 
-int binned_padded(int nb) {
-  TORCH_CHECK(nb >= 1 && nb <= kMaxBins, "gaussian_binned_sum: 1 <= nb <= ", kMaxBins, ", got ", nb);
-  return nb <= 4 ? 4 : nb <= 8 ? 8 : nb <= 16 ? 16 : 32;
-}
-
-#define MG_DISPATCH_BINNED(NBP, ...)                        \
-  switch (NBP) {                                            \
-    case 4: { constexpr int NB = 4; __VA_ARGS__; break; }   \
-    case 8: { constexpr int NB = 8; __VA_ARGS__; break; }   \
-    case 16: { constexpr int NB = 16; __VA_ARGS__; break; } \
-    default: { constexpr int NB = 32; __VA_ARGS__; break; } \
-  }
-
-bool aligned16(const void* p) { return aligned_to(p, 16); }
-
-// Workgroups that fill the chip once (occupancy x CU count of the device), per kernel.
-template <auto Kernel>
-int64_t chip_blocks() {
-  static int64_t cap = resident_blocks(reinterpret_cast<const void*>(Kernel), kBinThreads);
-  return cap;
-}
-
 template <auto Kernel>
 void launch_bwd(const BinnedArgs& a, BinnedGrad& o, const torch::Tensor& like, bool red_sig,
                 bool red_w, hipStream_t stream) {
@@ -274,35 +211,13 @@ void launch_bwd(const BinnedArgs& a, BinnedGrad& o, const torch::Tensor& like, b
                        red_w ? o.dw : nullptr);
 }
 
-BinnedArgs make_args(const torch::Tensor& mu, const torch::Tensor& sigma,
-                     const c10::optional<torch::Tensor>& w, const std::vector<double>& edges) {
-  check_dev(mu, "mu", at::kFloat);
-  check_dev(sigma, "sigma", at::kFloat);
-  BinnedArgs a;
-  a.n = mu.numel();
-  a.nb = (int)edges.size() - 1;
-  binned_padded(a.nb);
-  for (int e = 1; e <= a.nb; ++e)
-    TORCH_CHECK(edges[e] > edges[e - 1], "gaussian_binned_sum: edges must be strictly increasing");
-  for (int e = 0; e <= kMaxBins; ++e) a.edge[e] = (float)edges[std::min(e, a.nb)];
-  TORCH_CHECK(sigma.numel() == a.n || sigma.numel() == 1, "sigma must have N elements or one");
-  a.mu = mu.data_ptr<float>();
-  a.sigma = sigma.data_ptr<float>();
-  a.sig_b = sigma.numel() == 1 && a.n != 1;
-  a.w = nullptr;
-  a.w_b = 0;
-  if (w.has_value() && w->defined()) {
-    check_dev(*w, "weights", at::kFloat);
-    TORCH_CHECK(w->numel() == a.n || w->numel() == 1, "weights must have N elements or one");
-    a.w = w->data_ptr<float>();
-    a.w_b = w->numel() == 1 && a.n != 1;
-  }
-  a.vec = aligned16(a.mu) && (a.sig_b || aligned16(a.sigma)) &&
-          (a.w == nullptr || a.w_b || aligned16(a.w));
-  return a;
-}
-
 }  // namespace
+
+void launch_binned_reduce(const float* slab, int64_t rows, int ncols, float* out_a, int na,
+                          float* out_b, hipStream_t stream) {
+  hipLaunchKernelGGL(binned_reduce_kernel, dim3(1), dim3(kRedThreads), 0, stream, slab, rows, ncols,
+                     out_a, na, out_b);
+}
 
 torch::Tensor binned_forward(torch::Tensor mu, torch::Tensor sigma, c10::optional<torch::Tensor> w,
                              std::vector<double> edges) {

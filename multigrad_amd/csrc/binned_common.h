@@ -1,7 +1,9 @@
-// Device helpers shared by the Gaussian-binned-sum ops (binned.hip, binned2d.hip): the edge
-// CDF, guarded vector loads of per-object operands and the fixed-order slab column sum.
+// Device helpers shared by the Gaussian-binned-sum ops (binned.hip, binned_hvp.hip,
+// binned2d.hip, binned_multi.hip): the edge CDF, guarded vector loads of per-object operands,
+// the fixed-order slab column sum and the operands of the one-axis op.
 #pragma once
 #include "common.h"
+#include "smf_device.h"
 
 namespace mg {
 
@@ -116,6 +118,47 @@ __device__ __forceinline__ bool slab_column_sum(const float* slab, int64_t rows,
   }
   total = part[threadIdx.x];
   return (int)threadIdx.x < ncols;
+}
+
+// The operands of the one-axis op (binned.hip, binned_hvp.hip).
+struct BinnedArgs {
+  const float* mu;
+  const float* sigma;
+  const float* w;  // nullptr: every weight is 1
+  int64_t n;
+  int nb;     // real bins (<= the padded template count)
+  int sig_b;  // sigma has one element
+  int w_b;    // w has one element
+  int vec;    // every input pointer is 16-byte aligned
+  float edge[kMaxBins + 1];
+};
+
+// Four consecutive objects of quad q: mean, 1/sigma and weight.  A full quad of aligned
+// inputs is read with one 16-byte load per operand; a misaligned view and the last N % 4
+// objects take guarded scalar loads (never past the end).  Objects beyond N get weight 0.
+__device__ __forceinline__ void load_quad(const BinnedArgs& a, int64_t q, float (&m)[4],
+                                          float (&inv)[4], float (&wt)[4]) {
+  const int64_t i0 = q * 4;
+  float s[4];
+  if (a.vec && i0 + 4 <= a.n) {
+    wide_load<4>(a.mu, i0, m);
+    if (a.sig_b) splat(a.sigma[0], s);
+    else wide_load<4>(a.sigma, i0, s);
+    if (a.w == nullptr) splat(1.0f, wt);
+    else if (a.w_b) splat(a.w[0], wt);
+    else wide_load<4>(a.w, i0, wt);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t i = i0 + j;
+      const bool ok = i < a.n;
+      m[j] = ok ? a.mu[i] : 0.0f;
+      s[j] = ok ? a.sigma[a.sig_b ? 0 : i] : 1.0f;
+      wt[j] = !ok ? 0.0f : a.w == nullptr ? 1.0f : a.w[a.w_b ? 0 : i];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) inv[j] = 1.0f / s[j];
 }
 
 }  // namespace mg

@@ -405,6 +405,101 @@ class OnePointModel(_OptimizerFrontEnds):
             return detach_tree(loss_out), grad
         return grad
 
+    # ------------------------------------------------------------------ second order
+    def calc_hvp_from_params(self, params, vector, randkey=None):
+        """Hessian of the all-rank loss at ``params`` times ``vector``; identical on every rank.
+
+        The distributed chain rule at second order: with ``S = sum_r s_r(theta)``, ``J_r`` the
+        Jacobian of this rank's partial sumstats and ``c = dl/dS``,
+
+            H v = sum_r [ d/dtheta (J_r^T c) v  +  J_r^T (d2l/dS2) (sum_r' J_r' v) ]
+
+        from one run of the hooks: ``J_r v`` by the double-VJP trick, then exact second
+        derivatives of the hooks by autograd (every op the hooks use must be twice
+        differentiable; ``gaussian_binned_sum`` and the group ops are).  Collectives per
+        product: two of the sumstats' size, one of the parameters'.
+        """
+        return self._hvp_graph(params, randkey)(vector)
+
+    def calc_hessian_from_params(self, params, randkey=None):
+        """Dense ``[ndim, ndim]`` Hessian of the all-rank loss at ``params``, identical on every
+        rank: ``ndim`` Hessian-vector products (:meth:`calc_hvp_from_params`, one per unit
+        vector; the hooks run once and the loss cotangent is shared), symmetrised as
+        ``(H + H^T)/2``.  The cost is ``ndim`` second-order backward passes and ``ndim^2``
+        memory, so this is meant for tens to thousands of parameters (covariances and error
+        bars at an optimum); larger problems use the products directly."""
+        hvp = self._hvp_graph(params, randkey)
+        p = hvp.params
+        cols = []
+        for i in range(p.numel()):
+            v = torch.zeros_like(p).reshape(-1)
+            v[i] = 1.0
+            cols.append(hvp(v.reshape(p.shape)).reshape(-1))
+        if not cols:
+            return p.new_zeros(0, 0)
+        H = torch.stack(cols, dim=1)
+        return 0.5 * (H + H.T)
+
+    def _hvp_graph(self, params, randkey=None):
+        """Run the hooks once (aux and ``randkey`` as in ``_vjp``) and return ``hvp(vector)``,
+        which can be called for several vectors; ``hvp.params`` is the parameter tensor."""
+        rk = _rk(randkey)
+        p = self._params(params).detach().requires_grad_(True)
+        with torch.enable_grad():
+            out = self.calc_partial_sumstats_from_params(p, **rk)
+            partial, saux = out if self.sumstats_func_has_aux else (out, None)
+            partial = torch.as_tensor(partial)
+            # (1) total sumstats and the loss cotangent on them, kept differentiable
+            total = self._allreduce(partial).requires_grad_(True)
+            args = (total, saux) if self.sumstats_func_has_aux else (total,)
+            loss_out = self.calc_loss_from_sumstats(*args, **rk)
+            loss = loss_out[0] if self.loss_func_has_aux else loss_out
+            cot = None
+            if torch.is_tensor(loss) and loss.requires_grad:
+                (cot,) = torch.autograd.grad(loss, total, create_graph=True, allow_unused=True)
+            cot_is_const = cot is None or not cot.requires_grad  # the loss is linear in S
+            cot_val = torch.zeros_like(total) if cot is None else cot.detach()
+            # the local pullbacks u -> J^T u (for J v) and J^T cot, kept differentiable
+            jt_u = jt_c = None
+            if partial.requires_grad:
+                u = torch.zeros_like(partial).requires_grad_(True)
+                (jt_u,) = torch.autograd.grad(partial, p, u, create_graph=True, allow_unused=True)
+                (jt_c,) = torch.autograd.grad(partial, p, cot_val, create_graph=True,
+                                              allow_unused=True)
+
+        def hvp(vector):
+            v = torch.as_tensor(vector).to(p).reshape(p.shape)
+            hv = torch.zeros_like(p)
+            if jt_u is not None and jt_u.requires_grad:
+                with torch.enable_grad():
+                    # (2) J v = d/du <J^T u, v>, summed over the ranks
+                    (jv,) = torch.autograd.grad(jt_u, u, v, retain_graph=True, allow_unused=True)
+                    jv = self._allreduce(torch.zeros_like(partial) if jv is None else jv)
+                    # (3) q = (d2l/dS2) J v: zero when the loss is linear in the sumstats
+                    q = None
+                    if not cot_is_const:
+                        (q,) = torch.autograd.grad(cot, total, jv, retain_graph=True,
+                                                   allow_unused=True)
+                    # (4) d/dtheta <J^T cot, v> (zero when the sumstats are linear in the
+                    # parameters) + J^T q
+                    if jt_c is not None and jt_c.requires_grad:
+                        (t1,) = torch.autograd.grad(jt_c, p, v, retain_graph=True,
+                                                    allow_unused=True)
+                        if t1 is not None:
+                            hv = hv + t1
+                    if q is not None:
+                        (t2,) = torch.autograd.grad(partial, p, q, retain_graph=True,
+                                                    allow_unused=True)
+                        if t2 is not None:
+                            hv = hv + t2
+            else:
+                # no local dependence on the parameters: this rank still joins the collectives
+                self._allreduce(torch.zeros_like(partial))
+            return self._allreduce(hv)
+
+        hvp.params = p.detach()
+        return hvp
+
     # ------------------------------------------------------------------ identity
     def __hash__(self):
         name = getattr(self.comm, "name", None)

@@ -11,6 +11,11 @@ fixed-order reduce; backward: one recomputing pass, no residuals, no float atomi
 results are bitwise reproducible).  Every other dtype or device runs the same
 ``autograd.Function`` with the forward and the analytic backward written in torch ops,
 chunked over objects so that peak memory is ``O(chunk * nb)``.
+
+The op is twice differentiable: the first backward is itself an ``autograd.Function`` of
+``(mu, sigma, w, g)`` whose backward (``csrc/binned_hvp.hip`` for float32 device tensors, the
+same formulas in chunked torch ops otherwise) is one more recomputing pass.  Third order
+raises torch's ``once_differentiable`` error.
 """
 from __future__ import annotations
 
@@ -107,38 +112,139 @@ def _native(mu: torch.Tensor) -> bool:
     return mu.is_cuda and mu.dtype == torch.float32
 
 
-class _GaussianBinnedSum(torch.autograd.Function):
+def _torch_backward2(mu, sigma, w, edges: Tuple[float, ...], g, a, b, c, need, chunk: int):
+    """Gradients of sum_i (a_i dmu_i + b_i dsigma_i + c_i dw_i) with respect to (mu, sigma, w,
+    g), the kernel's formulas (csrc/binned_hvp.hip) in torch ops: with the moments
+    M_n = sum_e h_e z_e^n phi(z_e),
+    d/dmu = (w/sigma^2)[-a M1 + b (M0 - M2)] - c M0/sigma,
+    d/dsigma = (w/sigma^2)[a (M0 - M2) + b (2 M1 - M3)] - c M1/sigma,
+    d/dw = -(a M0 + b M1)/sigma and d/dg_k = T_{k+1} - T_k with
+    T_e = sum_i [-(w_i/sigma_i)(a_i + b_i z_ie) phi(z_ie) + c_i Phi(z_ie)].
+    A cotangent that is None is a zero; a broadcast operand has a one-element cotangent and
+    receives the sum over objects."""
+    n = mu.numel()
+    e = torch.tensor(edges, dtype=mu.dtype, device=mu.device)
+    zero = g.new_zeros(1)
+    h = torch.cat([zero, g]) - torch.cat([g, zero])
+    obj = need[0] or need[1] or need[2]
+
+    def alloc(t):
+        return torch.zeros_like(t) if t.numel() == 1 else torch.empty_like(t)
+
+    gmu = torch.empty_like(mu) if need[0] else None
+    gsig = alloc(sigma) if need[1] else None
+    gw = alloc(w) if need[2] else None
+    T = torch.zeros_like(e) if need[3] else None
+    for lo in range(0, n, chunk):
+        hi = min(lo + chunk, n)
+        s = _bcast(sigma, lo, hi)
+        z = (e[None, :] - mu[lo:hi, None]) / s[:, None]
+        phi = torch.exp(-0.5 * z * z) * _INV_SQRT_2PI
+        ws = 1.0 / s if w is None else _bcast(w, lo, hi) / s
+        ac = None if a is None else a[lo:hi]
+        bc = None if b is None else _bcast(b, lo, hi)
+        cc = None if c is None else _bcast(c, lo, hi)
+        if obj:
+            hphi = h[None, :] * phi
+            M0 = hphi.sum(1)
+            M1 = (hphi * z).sum(1)
+            M2 = (hphi * z * z).sum(1)
+            dm = torch.zeros_like(M0)
+            ds = torch.zeros_like(M0)
+            dw = torch.zeros_like(M0)
+            if ac is not None:
+                dm = dm - ws / s * ac * M1
+                ds = ds + ws / s * ac * (M0 - M2)
+                dw = dw - ac * M0 / s
+            if bc is not None:
+                M3 = (hphi * z * z * z).sum(1)
+                dm = dm + ws / s * bc * (M0 - M2)
+                ds = ds + ws / s * bc * (2.0 * M1 - M3)
+                dw = dw - bc * M1 / s
+            if cc is not None:
+                dm = dm - cc * M0 / s
+                ds = ds - cc * M1 / s
+            if need[0]:
+                gmu[lo:hi] = dm
+            for out, val in ((gsig, ds), (gw, dw)):
+                if out is None:
+                    continue
+                if out.numel() == 1:
+                    out += val.sum()
+                else:
+                    out[lo:hi] = val
+        if need[3]:
+            if ac is not None:
+                T -= ((ws * ac)[:, None] * phi).sum(0)
+            if bc is not None:
+                T -= ((ws * bc)[:, None] * (z * phi)).sum(0)
+            if cc is not None:
+                T += (torch.broadcast_to(cc, (hi - lo,))[:, None] * torch.special.ndtr(z)).sum(0)
+    gg = T[1:] - T[:-1] if need[3] else None
+    return gmu, gsig, gw, gg
+
+
+class _GaussianBinnedSumBackward(torch.autograd.Function):
+    """The first backward as a function of (mu, sigma, w, g), so that it can be differentiated
+    once more.  All tensors are flat and contiguous; ``need`` selects which of (dmu, dsigma,
+    dw) are computed (the others are None)."""
+
     @staticmethod
-    def forward(ctx, mu, sigma, w, edges, chunk):
+    def forward(ctx, mu, sigma, w, g, edges, chunk, need):
+        ctx.set_materialize_grads(False)
         ctx.edges, ctx.chunk = edges, chunk
-        ctx.shapes = (mu.shape, sigma.shape, None if w is None else w.shape)
-        mu_f = mu.detach().reshape(-1).contiguous()
-        sig_f = sigma.detach().reshape(-1).contiguous()
-        w_f = None if w is None else w.detach().reshape(-1).contiguous()
-        ctx.save_for_backward(mu_f, sig_f, w_f)
-        if mu_f.numel() == 0:
-            return mu_f.new_zeros(len(edges) - 1)
-        if _native(mu_f):
-            return ext().binned_forward(mu_f, sig_f, w_f, list(edges))
-        return _torch_forward(mu_f, sig_f, w_f, edges, chunk)
+        ctx.save_for_backward(mu, sigma, w, g)
+        if mu.numel() == 0:
+            grads = [torch.zeros_like(t) if k else None for t, k in zip((mu, sigma, w), need)]
+        elif _native(mu):
+            grads = ext().binned_backward(mu, sigma, w, list(edges), g, *need)
+        else:
+            grads = _torch_backward(mu, sigma, w, edges, g, need, chunk)
+        return tuple(grads)
 
     @staticmethod
     @once_differentiable
+    def backward(ctx, a, b, c):
+        mu, sigma, w, g = ctx.saved_tensors
+        need = (ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+                w is not None and ctx.needs_input_grad[2], ctx.needs_input_grad[3])
+        if not any(need) or (a is None and b is None and c is None):
+            return (None,) * 7
+        if mu.numel() == 0:
+            grads = [torch.zeros_like(t) if k else None for t, k in zip((mu, sigma, w, g), need)]
+        elif _native(mu):
+            a, b, c = (None if t is None else t.contiguous() for t in (a, b, c))
+            grads = ext().binned_backward2(mu, sigma, w, list(ctx.edges), g, a, b, c, *need)
+        else:
+            grads = _torch_backward2(mu, sigma, w, ctx.edges, g, a, b, c, need, ctx.chunk)
+        return (*grads, None, None, None)
+
+
+class _GaussianBinnedSum(torch.autograd.Function):
+    """The forward, on flat contiguous operands (gaussian_binned_sum flattens them with
+    differentiable views, so that the saved tensors are the caller's graph)."""
+
+    @staticmethod
+    def forward(ctx, mu, sigma, w, edges, chunk):
+        ctx.edges, ctx.chunk = edges, chunk
+        ctx.save_for_backward(mu, sigma, w)
+        if mu.numel() == 0:
+            return mu.new_zeros(len(edges) - 1)
+        if _native(mu):
+            return ext().binned_forward(mu, sigma, w, list(edges))
+        return _torch_forward(mu, sigma, w, edges, chunk)
+
+    @staticmethod
     def backward(ctx, g):
         mu, sigma, w = ctx.saved_tensors
         need = (ctx.needs_input_grad[0], ctx.needs_input_grad[1],
                 w is not None and ctx.needs_input_grad[2])
         if not any(need):
             return None, None, None, None, None
-        if mu.numel() == 0:
-            grads = [torch.zeros_like(t) if k else None for t, k in zip((mu, sigma, w), need)]
-        elif _native(mu):
-            grads = ext().binned_backward(mu, sigma, w, list(ctx.edges), g.contiguous().float(),
-                                          *need)
-        else:
-            grads = _torch_backward(mu, sigma, w, ctx.edges, g.to(mu.dtype), need, ctx.chunk)
-        out = [None if gr is None else gr.reshape(shp) for gr, shp in zip(grads, ctx.shapes)]
-        return out[0], out[1], out[2], None, None
+        g = g.contiguous().float() if _native(mu) else g.to(mu.dtype)
+        dmu, dsigma, dw = _GaussianBinnedSumBackward.apply(mu, sigma, w, g, ctx.edges, ctx.chunk,
+                                                           need)
+        return dmu, dsigma, dw, None, None
 
 
 def gaussian_binned_sum(mu: torch.Tensor, sigma: torch.Tensor, edges: Sequence[float],
@@ -157,11 +263,18 @@ def gaussian_binned_sum(mu: torch.Tensor, sigma: torch.Tensor, edges: Sequence[f
     weights : optional tensor of N elements or one element (broadcast); ``None`` means 1.
     chunk : objects per chunk of the torch path (default 65536); ignored by the kernels.
 
-    Returns the ``[nb]`` tensor of bin sums in ``mu``'s dtype, differentiable (first order)
-    with respect to ``mu``, ``sigma`` and ``weights``.  float32 device inputs run the HIP
+    Returns the ``[nb]`` tensor of bin sums in ``mu``'s dtype, differentiable to second order
+    (``create_graph=True``, ``torch.autograd.functional.hessian``,
+    ``OnePointModel.calc_hvp_from_params``) with respect to ``mu``, ``sigma`` and ``weights``;
+    with ``create_graph=False`` the first-order results are bitwise those of the first-order
+    kernels alone.  float32 device inputs run the HIP
     kernels (absolute accuracy of the float32 erf: each edge CDF within ~1.6e-7, so a bin is
     within ``2.2e-7 * sum_i |w_i|``; bitwise reproducible; no host sync, graph-capturable);
-    every other dtype or device runs chunked torch ops in the input dtype.
+    every other dtype or device runs chunked torch ops in the input dtype.  Second-order
+    outputs of the kernels carry no derived float32 bound; their contract is relative to the
+    float32 ``ndtr`` composite under torch's double backward: per output, against float64 on
+    the float32-rounded inputs, ``max|op - ref| <= 2 max|composite - ref| + 2e-5 max|ref|``
+    (the factor 2 is measured, not derived: profiles/binned_hvp/README.md).
     """
     if not isinstance(mu, torch.Tensor) or not isinstance(sigma, torch.Tensor):
         raise TypeError("gaussian_binned_sum: mu and sigma must be tensors")
@@ -178,4 +291,5 @@ def gaussian_binned_sum(mu: torch.Tensor, sigma: torch.Tensor, edges: Sequence[f
             raise ValueError(f"gaussian_binned_sum: {name} must have mu's dtype and device")
     if not mu.dtype.is_floating_point:
         raise ValueError("gaussian_binned_sum: floating-point inputs required")
-    return _GaussianBinnedSum.apply(mu, sigma, weights, e, int(chunk or _CHUNK))
+    flat = [None if t is None else t.reshape(-1).contiguous() for t in (mu, sigma, weights)]
+    return _GaussianBinnedSum.apply(*flat, e, int(chunk or _CHUNK))

@@ -178,8 +178,8 @@ def gaussian_binned_sum_2d(mu_x: torch.Tensor, sigma_x: torch.Tensor, mu_y: torc
     chunk : objects per chunk of the torch path (default 65536); ignored by the kernels.
 
     Returns the ``[nbx, nby]`` tensor of cell sums in ``mu_x``'s dtype, differentiable (first
-    order) with respect to each of the five tensor operands; a broadcast operand receives the
-    sum over objects.  float32 device inputs run the HIP kernels: no host synchronisation,
+    order only; second order is offered by ``gaussian_binned_sum`` alone) with respect to each
+    of the five tensor operands; a broadcast operand receives the sum over objects.  float32 device inputs run the HIP kernels: no host synchronisation,
     launches on the current stream (graph-capturable), bitwise reproducible, and per cell
     ``|out - exact| <= 4.4e-7 * sum_i |w_i| + 2e-5 * |exact|`` (both factors of a cell carry
     the 2.2e-7 absolute error of the float32 Phi difference; the second term is float32

@@ -180,8 +180,8 @@ def gaussian_binned_sum_multi(mu: torch.Tensor, sigma: torch.Tensor, edges: Sequ
     chunk : objects per chunk of the torch path (default 65536); ignored by the kernels.
 
     Returns the ``[C, nb]`` tensor in ``mu``'s dtype; row ``c`` is the value of
-    ``gaussian_binned_sum(mu, sigma, edges, weights[c])``.  Differentiable (first order) with
-    respect to ``mu``, ``sigma`` and every weight tensor that requires grad; a broadcast
+    ``gaussian_binned_sum(mu, sigma, edges, weights[c])``.  Differentiable (first order only;
+    second order is offered by ``gaussian_binned_sum`` alone) with respect to ``mu``, ``sigma`` and every weight tensor that requires grad; a broadcast
     operand receives the sum over objects, an operand that does not require grad costs no
     store, and a tensor given in several channels gets the sum of its channel gradients.
     ``N == 0`` gives zeros.
