@@ -135,6 +135,10 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> binned_ba
     torch::Tensor mu, torch::Tensor sigma, c10::optional<torch::Tensor> w, std::vector<double> edges,
     torch::Tensor g, c10::optional<torch::Tensor> ca, c10::optional<torch::Tensor> cb,
     c10::optional<torch::Tensor> cc, bool need_mu, bool need_sigma, bool need_w, bool need_g);
+// binned_jvp.hip
+torch::Tensor binned_jvp(torch::Tensor mu, torch::Tensor sigma, c10::optional<torch::Tensor> w,
+                         std::vector<double> edges, c10::optional<torch::Tensor> tmu,
+                         c10::optional<torch::Tensor> tsigma, c10::optional<torch::Tensor> tw);
 // binned2d.hip
 torch::Tensor binned2d_forward(torch::Tensor mux, torch::Tensor sigx, torch::Tensor muy,
                                torch::Tensor sigy, c10::optional<torch::Tensor> w,
@@ -260,6 +264,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("binned_forward", &mg::binned_forward);
   m.def("binned_backward", &mg::binned_backward);
   m.def("binned_backward2", &mg::binned_backward2);
+  m.def("binned_jvp", &mg::binned_jvp);
   m.def("binned2d_forward", &mg::binned2d_forward);
   m.def("binned2d_backward", &mg::binned2d_backward);
   m.def("binned_multi_forward", &mg::binned_multi_forward);

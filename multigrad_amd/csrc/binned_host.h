@@ -1,5 +1,5 @@
 // Host-side helpers shared by the one-axis Gaussian-binned-sum translation units (binned.hip:
-// forward and first backward; binned_hvp.hip: second backward): checked arguments, the padded
+// forward and first backward; binned_hvp.hip: second backward; binned_jvp.hip: tangent): checked arguments, the padded
 // dispatch and the launcher of the slab reduce, which is instantiated in binned.hip.
 #pragma once
 #include "binned_common.h"
@@ -61,5 +61,9 @@ inline BinnedArgs make_args(const torch::Tensor& mu, const torch::Tensor& sigma,
 // workgroup.  Columns [0, na) go to out_a, column na to out_b (either may be null: dropped).
 void launch_binned_reduce(const float* slab, int64_t rows, int ncols, float* out_a, int na,
                           float* out_b, hipStream_t stream);
+
+// binned.hip: the forward, which binned_jvp.hip calls for a tangent of the weights alone.
+torch::Tensor binned_forward(torch::Tensor mu, torch::Tensor sigma, c10::optional<torch::Tensor> w,
+                             std::vector<double> edges);
 
 }  // namespace mg

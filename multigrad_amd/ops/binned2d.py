@@ -178,7 +178,10 @@ def gaussian_binned_sum_2d(mu_x: torch.Tensor, sigma_x: torch.Tensor, mu_y: torc
     chunk : objects per chunk of the torch path (default 65536); ignored by the kernels.
 
     Returns the ``[nbx, nby]`` tensor of cell sums in ``mu_x``'s dtype, differentiable (first
-    order only; second order is offered by ``gaussian_binned_sum`` alone) with respect to each
+    order only; second order and a forward-mode rule are offered by ``gaussian_binned_sum``
+    alone: under ``torch.autograd.forward_ad`` this op raises torch's ``NotImplementedError``,
+    and ``OnePointModel.calc_sumstats_jacobian_from_params`` then works in reverse mode) with
+    respect to each
     of the five tensor operands; a broadcast operand receives the sum over objects.  float32 device inputs run the HIP kernels: no host synchronisation,
     launches on the current stream (graph-capturable), bitwise reproducible, and per cell
     ``|out - exact| <= 4.4e-7 * sum_i |w_i| + 2e-5 * |exact|`` (both factors of a cell carry

@@ -181,7 +181,10 @@ def gaussian_binned_sum_multi(mu: torch.Tensor, sigma: torch.Tensor, edges: Sequ
 
     Returns the ``[C, nb]`` tensor in ``mu``'s dtype; row ``c`` is the value of
     ``gaussian_binned_sum(mu, sigma, edges, weights[c])``.  Differentiable (first order only;
-    second order is offered by ``gaussian_binned_sum`` alone) with respect to ``mu``, ``sigma`` and every weight tensor that requires grad; a broadcast
+    second order and a forward-mode rule are offered by ``gaussian_binned_sum``
+    alone: under ``torch.autograd.forward_ad`` this op raises torch's ``NotImplementedError``,
+    and ``OnePointModel.calc_sumstats_jacobian_from_params`` then works in reverse mode) with
+    respect to ``mu``, ``sigma`` and every weight tensor that requires grad; a broadcast
     operand receives the sum over objects, an operand that does not require grad costs no
     store, and a tensor given in several channels gets the sum of its channel gradients.
     ``N == 0`` gives zeros.

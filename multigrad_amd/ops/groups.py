@@ -187,6 +187,13 @@ def _transpose(op, plan, grads, needs, shapes):
     return (None, *out)
 
 
+def _tangents(raw, tangents, shapes):
+    """Forward mode of a linear op: the raw op applied to the tangents.  A missing (``None``)
+    tangent becomes zeros, since another operand of the same call has one."""
+    ref = next(t for t in tangents if t is not None)
+    return raw([ref.new_zeros(s) if t is None else t for t, s in zip(tangents, shapes)])
+
+
 class _Gather(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan, *values):
@@ -197,6 +204,10 @@ class _Gather(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         return _transpose(_SegmentSum, ctx.plan, grads, ctx.needs_input_grad[1:], ctx.shapes)
+
+    @staticmethod
+    def jvp(ctx, _plan, *tangents):
+        return _tangents(ctx.plan._gather_raw, tangents, ctx.shapes)
 
 
 class _SegmentSum(torch.autograd.Function):
@@ -209,6 +220,10 @@ class _SegmentSum(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         return _transpose(_Gather, ctx.plan, grads, ctx.needs_input_grad[1:], ctx.shapes)
+
+    @staticmethod
+    def jvp(ctx, _plan, *tangents):
+        return _tangents(ctx.plan._segment_sum_raw, tangents, ctx.shapes)
 
 
 def group_gather(plan: GroupIndex, *values: torch.Tensor) -> Tuple[torch.Tensor, ...]:

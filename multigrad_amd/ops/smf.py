@@ -787,7 +787,10 @@ def smf_sumstats(theta: torch.Tensor, shard: PopulationShard, bins: SmfBins,
     """Partial SMF of this rank's shard; differentiable w.r.t. interleaved ``theta``.
 
     ``theta`` holds ``(a_c, s_c)`` per population (``2 * npop`` values).  On a GPU this
-    runs the HIP kernels (float32); on CPU the PyTorch reference.
+    runs the HIP kernels (float32); on CPU the PyTorch reference.  The device op is
+    reverse mode only: under ``torch.autograd.forward_ad`` it raises torch's
+    ``NotImplementedError``, and ``OnePointModel.calc_sumstats_jacobian_from_params`` then
+    works in reverse mode.
     """
     if theta.device.type == "cuda":
         th = theta.reshape(-1)
