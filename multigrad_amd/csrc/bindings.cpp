@@ -157,6 +157,14 @@ std::vector<torch::Tensor> binned_multi_backward(torch::Tensor mu, torch::Tensor
                                                  std::vector<double> edges, torch::Tensor g,
                                                  bool need_mu, bool need_sigma,
                                                  std::vector<bool> need_w);
+// binned_group.hip
+torch::Tensor binned_group_forward(torch::Tensor sorted_ids, c10::optional<torch::Tensor> perm,
+                                   torch::Tensor mu, torch::Tensor sigma,
+                                   c10::optional<torch::Tensor> w, std::vector<double> edges,
+                                   int64_t num_groups);
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> binned_group_backward(
+    torch::Tensor ids, torch::Tensor mu, torch::Tensor sigma, c10::optional<torch::Tensor> w,
+    std::vector<double> edges, torch::Tensor g, bool need_mu, bool need_sigma, bool need_w);
 // groups.hip
 int64_t group_chunk();
 std::vector<torch::Tensor> group_gather(torch::Tensor ids, std::vector<torch::Tensor> values,
@@ -269,6 +277,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("binned2d_backward", &mg::binned2d_backward);
   m.def("binned_multi_forward", &mg::binned_multi_forward);
   m.def("binned_multi_backward", &mg::binned_multi_backward);
+  m.def("binned_group_forward", &mg::binned_group_forward);
+  m.def("binned_group_backward", &mg::binned_group_backward);
   m.def("group_chunk", &mg::group_chunk);
   m.def("group_gather", &mg::group_gather);
   m.def("group_segment_sum", &mg::group_segment_sum);

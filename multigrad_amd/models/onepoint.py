@@ -510,9 +510,10 @@ class OnePointModel(_OptimizerFrontEnds):
         ``mode="forward"``: ``ndim`` runs of the sumstats hook under
         ``torch.autograd.forward_ad`` with unit tangents (every op the hook applies to the
         parameters needs a forward rule: torch's own ops, ``gaussian_binned_sum`` and the
-        group ops have one; ``gaussian_binned_sum_2d``, ``gaussian_binned_sum_multi`` and
-        the SMF ops raise ``NotImplementedError``).  ``mode="reverse"``: one run of the hook
-        and one backward pass per sumstat, which works with every first-order op.
+        group ops have one; ``gaussian_binned_sum_2d``, ``gaussian_binned_sum_multi``,
+        ``gaussian_binned_sum_by_group`` and the SMF ops raise ``NotImplementedError``).
+        ``mode="reverse"``: one run of the hook and one backward pass per sumstat, which works
+        with every first-order op.
         ``mode="auto"`` (default): forward, and reverse if the hook meets an op without a
         forward rule.  Forward costs ``ndim`` runs of the hook and keeps no graph (peak
         memory of a ``no_grad`` evaluation); reverse costs one run and ``K`` backward passes.

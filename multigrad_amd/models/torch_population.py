@@ -24,7 +24,8 @@ from .onepoint import OnePointModel
 __all__ = ["TorchPopulationSMFModel", "StochasticTorchPopulationSMFModel",
            "BinnedPopulationSMFModel", "GroupedBinnedPopulationSMFModel",
            "JointBinnedPopulationSMFModel", "ConditionalBinnedPopulationSMFModel",
-           "torch_population_data", "joint_population_data", "conditional_population_data"]
+           "SampleBinnedPopulationSMFModel", "torch_population_data", "joint_population_data",
+           "conditional_population_data", "sample_population_data"]
 
 
 def torch_population_data(data: dict) -> dict:
@@ -223,6 +224,52 @@ def conditional_population_data(data: dict, seed: int = 0, **model_kwargs) -> di
                scale=scale, target=torch.ones_like(scale), eps=float(data["loss_eps"]),
                npop=int(data["npop"]))
     model = ConditionalBinnedPopulationSMFModel(aux_data=aux, **model_kwargs)
+    with torch.no_grad():
+        aux["target"] = model.calc_sumstats_from_params(
+            data["truth"].to(dev, torch.float32)).float()
+    return aux
+
+
+@dataclass(eq=False)
+class SampleBinnedPopulationSMFModel(GroupedBinnedPopulationSMFModel):
+    """The stellar-mass function once per sample (a redshift slice, a survey field) on
+    :func:`~multigrad_amd.ops.binned_group.gaussian_binned_sum_by_group`: every halo carries a
+    sample id next to its population id, and the sumstats are the ``nsamples * nb`` per-sample
+    SMFs, sample-major.  ``aux_data`` from :func:`sample_population_data`: the per-halo
+    ``sample`` ids, ``nsamples`` and ``scale`` / ``target`` of ``nsamples * nb`` entries (the
+    per-bin scale repeated per sample).  A second ``GroupIndex`` over the sample ids is built
+    once; they are unsorted, so that plan carries a permutation."""
+
+    def __post_init__(self):
+        super().__post_init__()
+        self.samples = GroupIndex(self.aux_data["sample"], self.aux_data["nsamples"])
+
+    def _sums(self, mu, sigma):
+        return self.samples.binned_sum(mu, sigma, self.edges)
+
+    def _sumstats(self, params, x):
+        d = self.aux_data
+        th = params.reshape(-1, 2)
+        a, sigma = self.groups.gather(th[:, 0], torch.pow(10.0, th[:, 1]))
+        return self._sums(x + a, sigma).reshape(-1) * d["scale"]
+
+
+def sample_population_data(data: dict, nsamples: int = 3, seed: int = 0) -> dict:
+    """``aux_data`` of :class:`SampleBinnedPopulationSMFModel` from
+    :func:`~multigrad_amd.models.population.make_population_data` output: every halo gets a
+    seeded, unsorted sample id in ``[0, nsamples)``, the per-bin scale is repeated per sample,
+    and the target is the model's own sumstats at ``data["truth"]``."""
+    sh = data["shard"]
+    bins = data["bins"]
+    dev = sh.x.device
+    gen = torch.Generator().manual_seed(3000 + seed)
+    sample = torch.randint(0, int(nsamples), (sh.x.numel(),), generator=gen).to(dev)
+    scale = torch.tensor(bins.scale, dtype=torch.float32, device=dev).repeat(int(nsamples))
+    aux = dict(x=sh.x.float(), pop=sh.pop.long(), sample=sample, nsamples=int(nsamples),
+               edges=torch.tensor(bins.edges, dtype=torch.float32, device=dev),
+               scale=scale, target=torch.ones_like(scale), eps=float(data["loss_eps"]),
+               npop=int(data["npop"]))
+    model = SampleBinnedPopulationSMFModel(aux_data=aux)
     with torch.no_grad():
         aux["target"] = model.calc_sumstats_from_params(
             data["truth"].to(dev, torch.float32)).float()

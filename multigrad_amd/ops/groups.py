@@ -140,6 +140,12 @@ class GroupIndex:
         _check_operands("segment_sum", self, per_object, self.n)
         return _SegmentSum.apply(self, *per_object)
 
+    def binned_sum(self, mu, sigma, edges, weights=None, *, chunk=None) -> torch.Tensor:
+        """The Gaussian-binned sum of every group, ``[num_groups, nb]``:
+        :func:`~multigrad_amd.ops.binned_group.gaussian_binned_sum_by_group` on this plan."""
+        from .binned_group import gaussian_binned_sum_by_group
+        return gaussian_binned_sum_by_group(self, mu, sigma, edges, weights, chunk=chunk)
+
     # ---- the raw ops (no autograd) ----
     def _native(self, t: torch.Tensor) -> bool:
         return t.is_cuda and t.dtype == torch.float32 and self.n < _INT32_MAX
