@@ -165,6 +165,12 @@ torch::Tensor binned_group_forward(torch::Tensor sorted_ids, c10::optional<torch
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> binned_group_backward(
     torch::Tensor ids, torch::Tensor mu, torch::Tensor sigma, c10::optional<torch::Tensor> w,
     std::vector<double> edges, torch::Tensor g, bool need_mu, bool need_sigma, bool need_w);
+// binned_fine.hip
+torch::Tensor binned_fine_forward(torch::Tensor mu, torch::Tensor sigma,
+                                  c10::optional<torch::Tensor> w, torch::Tensor edges);
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> binned_fine_backward(
+    torch::Tensor mu, torch::Tensor sigma, c10::optional<torch::Tensor> w, torch::Tensor edges,
+    torch::Tensor g, bool need_mu, bool need_sigma, bool need_w);
 // groups.hip
 int64_t group_chunk();
 std::vector<torch::Tensor> group_gather(torch::Tensor ids, std::vector<torch::Tensor> values,
@@ -279,6 +285,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("binned_multi_backward", &mg::binned_multi_backward);
   m.def("binned_group_forward", &mg::binned_group_forward);
   m.def("binned_group_backward", &mg::binned_group_backward);
+  m.def("binned_fine_forward", &mg::binned_fine_forward);
+  m.def("binned_fine_backward", &mg::binned_fine_backward);
   m.def("group_chunk", &mg::group_chunk);
   m.def("group_gather", &mg::group_gather);
   m.def("group_segment_sum", &mg::group_segment_sum);

@@ -16,6 +16,7 @@ import torch
 
 from ..ops.binned import gaussian_binned_sum
 from ..ops.binned2d import gaussian_binned_sum_2d
+from ..ops.binned_fine import FineBins
 from ..ops.binned_multi import gaussian_binned_sum_multi
 from ..ops.groups import GroupIndex
 from ..ops.smf import logmse_loss
@@ -24,8 +25,9 @@ from .onepoint import OnePointModel
 __all__ = ["TorchPopulationSMFModel", "StochasticTorchPopulationSMFModel",
            "BinnedPopulationSMFModel", "GroupedBinnedPopulationSMFModel",
            "JointBinnedPopulationSMFModel", "ConditionalBinnedPopulationSMFModel",
-           "SampleBinnedPopulationSMFModel", "torch_population_data", "joint_population_data",
-           "conditional_population_data", "sample_population_data"]
+           "SampleBinnedPopulationSMFModel", "FineBinnedPopulationSMFModel",
+           "torch_population_data", "joint_population_data", "conditional_population_data",
+           "sample_population_data", "fine_population_data"]
 
 
 def torch_population_data(data: dict) -> dict:
@@ -270,6 +272,61 @@ def sample_population_data(data: dict, nsamples: int = 3, seed: int = 0) -> dict
                scale=scale, target=torch.ones_like(scale), eps=float(data["loss_eps"]),
                npop=int(data["npop"]))
     model = SampleBinnedPopulationSMFModel(aux_data=aux)
+    with torch.no_grad():
+        aux["target"] = model.calc_sumstats_from_params(
+            data["truth"].to(dev, torch.float32)).float()
+    return aux
+
+
+@dataclass(eq=False)
+class FineBinnedPopulationSMFModel(GroupedBinnedPopulationSMFModel):
+    """The stellar-mass function in many fine bins on
+    :func:`~multigrad_amd.ops.binned_fine.gaussian_binned_sum_fine`: the same model with every
+    coarse bin split into equal parts, as one fits a finely binned SMF that is merged later
+    under several binnings.  ``aux_data`` from :func:`fine_population_data`: ``edges``,
+    ``scale`` and ``target`` of the fine bins (up to 4096).  The :class:`FineBins` plan is built
+    once from the host edges; a captured step never reads them back.  This model's widths
+    (0.1-0.3 dex over a range of 1 dex) make every halo reach every bin, the regime in which
+    calls of ``gaussian_binned_sum`` on 33-edge slices are faster (profiles/binned_fine): it is
+    here to exercise the op under the engines, not as its best case."""
+
+    def __post_init__(self):
+        super().__post_init__()
+        self.bins = FineBins(self.edges, device=self.aux_data["x"].device)
+
+    def _sums(self, mu, sigma):
+        return self.bins.sum(mu, sigma)
+
+    def _sumstats(self, params, x):
+        d = self.aux_data
+        th = params.reshape(-1, 2)
+        a, sigma = self.groups.gather(th[:, 0], torch.pow(10.0, th[:, 1]))
+        return self._sums(x + a, sigma) * d["scale"]
+
+
+def fine_population_data(data: dict, refine: int = 8) -> dict:
+    """``aux_data`` of :class:`FineBinnedPopulationSMFModel` from
+    :func:`~multigrad_amd.models.population.make_population_data` output: every coarse bin is
+    split into ``refine`` equal bins (every ``refine``-th fine edge is the coarse edge itself,
+    so sums of ``refine`` consecutive fine bins are the coarse bins), the per-bin scale
+    ``1 / (volume * width)`` follows the fine widths, and the target is the model's own
+    sumstats at ``data["truth"]``."""
+    sh = data["shard"]
+    bins = data["bins"]
+    dev = sh.x.device
+    refine = int(refine)
+    if refine < 1:
+        raise ValueError("fine_population_data: refine must be at least 1")
+    coarse = torch.tensor(bins.edges, dtype=torch.float64)
+    frac = torch.arange(refine, dtype=torch.float64) / refine
+    inner = coarse[:-1, None] + (coarse[1:] - coarse[:-1])[:, None] * frac[None, :]
+    edges = torch.cat([inner.reshape(-1), coarse[-1:]]).float()
+    scale = (torch.tensor(bins.scale, dtype=torch.float64) * refine).float()
+    scale = scale.repeat_interleave(refine).to(dev)
+    aux = dict(x=sh.x.float(), pop=sh.pop.long(), edges=edges.to(dev), scale=scale,
+               target=torch.ones_like(scale), eps=float(data["loss_eps"]),
+               npop=int(data["npop"]), refine=refine)
+    model = FineBinnedPopulationSMFModel(aux_data=aux)
     with torch.no_grad():
         aux["target"] = model.calc_sumstats_from_params(
             data["truth"].to(dev, torch.float32)).float()

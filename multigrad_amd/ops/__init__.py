@@ -2,8 +2,8 @@
 from ._ext import available, ext
 
 __all__ = ["available", "ext", "gaussian_binned_sum", "gaussian_binned_sum_2d",
-           "gaussian_binned_sum_multi", "gaussian_binned_sum_by_group", "GroupIndex",
-           "group_gather", "segment_sum"]
+           "gaussian_binned_sum_multi", "gaussian_binned_sum_by_group",
+           "gaussian_binned_sum_fine", "FineBins", "GroupIndex", "group_gather", "segment_sum"]
 
 
 def __getattr__(name):  # lazy: importing the package loads no op module and no device
@@ -19,6 +19,9 @@ def __getattr__(name):  # lazy: importing the package loads no op module and no 
     if name == "gaussian_binned_sum_by_group":
         from .binned_group import gaussian_binned_sum_by_group
         return gaussian_binned_sum_by_group
+    if name in ("gaussian_binned_sum_fine", "FineBins"):
+        from . import binned_fine
+        return getattr(binned_fine, name)
     if name in ("GroupIndex", "group_gather", "segment_sum"):
         from . import groups
         return getattr(groups, name)
