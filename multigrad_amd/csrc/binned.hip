@@ -24,14 +24,6 @@ namespace mg {
 
 namespace {
 
-struct BinnedGrad {
-  const float* g;  // [nb] cotangent
-  float* dmu;      // [n]
-  float* dsigma;   // [n], or [1] when sigma is broadcast
-  float* dw;       // [n], or [1] when w is broadcast
-  float* slab;     // [blocks, 2] partial sums of the broadcast gradients (col 0 sigma, col 1 w)
-};
-
 template <int NB>
 __global__ __launch_bounds__(kBinThreads) void binned_fwd_kernel(BinnedArgs a, float* slab,
                                                                  float* out, int direct) {
@@ -70,24 +62,6 @@ __global__ __launch_bounds__(kBinThreads) void binned_fwd_kernel(BinnedArgs a, f
     } else {
 #pragma unroll
       for (int k = 0; k < NB; ++k) slab[(int64_t)blockIdx.x * NB + k] = acc[k];
-    }
-  }
-}
-
-// Fixed-order sum of slab rows [rows, ncols] (ncols a power of two <= 32) by one workgroup
-// (slab_column_sum).  Columns [0, na) go to out_a, column na to out_b (either may be null:
-// the column is dropped).
-__global__ __launch_bounds__(kRedThreads) void binned_reduce_kernel(const float* slab, int64_t rows,
-                                                                    int ncols, float* out_a, int na,
-                                                                    float* out_b) {
-  __shared__ float part[kRedThreads];
-  float t;
-  if (slab_column_sum(slab, rows, ncols, 0, ncols, part, t)) {
-    const int k = threadIdx.x;
-    if (k < na) {
-      if (out_a) out_a[k] = t;
-    } else if (k == na && out_b) {
-      out_b[0] = t;
     }
   }
 }
@@ -138,7 +112,6 @@ __global__ __launch_bounds__(kBinThreads) void binned_bwd_kernel(BinnedArgs a, B
       }
     }
     const int64_t i0 = q * 4;
-    const bool full = i0 + 4 <= a.n;
     float dm[4], ds[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -147,99 +120,25 @@ __global__ __launch_bounds__(kBinThreads) void binned_bwd_kernel(BinnedArgs a, B
       ds[j] = c * B[j];
       if (i0 + j >= a.n) C[j] = 0.0f;
     }
-    if constexpr (GMU) {
-      if (full) {
-        *reinterpret_cast<float4*>(o.dmu + i0) = make_float4(dm[0], dm[1], dm[2], dm[3]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (i0 + j < a.n) o.dmu[i0 + j] = dm[j];
-      }
-    }
-    if constexpr (GSIG) {
-      if (red_sig) {
-        rs[0] += (ds[0] + ds[1]) + (ds[2] + ds[3]);
-      } else if (full) {
-        *reinterpret_cast<float4*>(o.dsigma + i0) = make_float4(ds[0], ds[1], ds[2], ds[3]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (i0 + j < a.n) o.dsigma[i0 + j] = ds[j];
-      }
-    }
-    if constexpr (GW) {
-      if (red_w) {
-        rs[1] += (C[0] + C[1]) + (C[2] + C[3]);
-      } else if (full) {
-        *reinterpret_cast<float4*>(o.dw + i0) = make_float4(C[0], C[1], C[2], C[3]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (i0 + j < a.n) o.dw[i0 + j] = C[j];
-      }
-    }
+    if constexpr (GMU) store_group<4>(o.dmu, i0, a.n, dm);
+    if constexpr (GSIG) put_quad(red_sig, rs[0], o.dsigma, i0, a.n, ds);
+    if constexpr (GW) put_quad(red_w, rs[1], o.dw, i0, a.n, C);
   }
-  if (red_sig || red_w) {  // uniform over the grid
-    block_sum_n<2>(rs, red);
-    if (threadIdx.x == 0) {
-      if (direct) {
-        if (red_sig) o.dsigma[0] = rs[0];
-        if (red_w) o.dw[0] = rs[1];
-      } else {
-        o.slab[(int64_t)blockIdx.x * 2 + 0] = rs[0];
-        o.slab[(int64_t)blockIdx.x * 2 + 1] = rs[1];
-      }
-    }
-  }
-}
-
-template <auto Kernel>
-void launch_bwd(const BinnedArgs& a, BinnedGrad& o, const torch::Tensor& like, bool red_sig,
-                bool red_w, hipStream_t stream) {
-  const int64_t need = ((a.n + 3) / 4 + kBinThreads - 1) / kBinThreads;
-  const int64_t blocks = std::min(need, chip_blocks<Kernel>());
-  const bool two = (red_sig || red_w) && blocks > 1;
-  torch::Tensor slab;
-  if (two) {
-    slab = torch::empty({blocks, 2}, like.options());
-    o.slab = slab.data_ptr<float>();
-  }
-  hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(kBinThreads), 0, stream, a, o, blocks == 1 ? 1 : 0);
-  if (two)
-    hipLaunchKernelGGL(binned_reduce_kernel, dim3(1), dim3(kRedThreads), 0, stream,
-                       (const float*)o.slab, blocks, 2, red_sig ? o.dsigma : nullptr, 1,
-                       red_w ? o.dw : nullptr);
+  finish_broadcast(rs, red, red_sig, red_w, o.dsigma, o.dw, o.slab, direct);
 }
 
 }  // namespace
-
-void launch_binned_reduce(const float* slab, int64_t rows, int ncols, float* out_a, int na,
-                          float* out_b, hipStream_t stream) {
-  hipLaunchKernelGGL(binned_reduce_kernel, dim3(1), dim3(kRedThreads), 0, stream, slab, rows, ncols,
-                     out_a, na, out_b);
-}
 
 torch::Tensor binned_forward(torch::Tensor mu, torch::Tensor sigma, c10::optional<torch::Tensor> w,
                              std::vector<double> edges) {
   BinnedArgs a = make_args(mu, sigma, w, edges);
   TORCH_CHECK(a.n > 0, "binned_forward: empty input");
-  const int nbp = binned_padded(a.nb);
+  const int nbp = padded_bins(a.nb, "gaussian_binned_sum");
   auto out = torch::empty({a.nb}, mu.options());
   auto stream = at::hip::getCurrentHIPStream();
-  const int64_t need = ((a.n + 3) / 4 + kBinThreads - 1) / kBinThreads;
   MG_DISPATCH_BINNED(nbp, {
-    const int64_t blocks = std::min(need, chip_blocks<binned_fwd_kernel<NB>>());
-    if (blocks == 1) {
-      hipLaunchKernelGGL(binned_fwd_kernel<NB>, dim3(1), dim3(kBinThreads), 0, stream, a,
-                         (float*)nullptr, out.data_ptr<float>(), 1);
-    } else {
-      auto slab = torch::empty({blocks, (int64_t)NB}, mu.options());
-      hipLaunchKernelGGL(binned_fwd_kernel<NB>, dim3(blocks), dim3(kBinThreads), 0, stream, a,
-                         slab.data_ptr<float>(), (float*)nullptr, 0);
-      hipLaunchKernelGGL(binned_reduce_kernel, dim3(1), dim3(kRedThreads), 0, stream,
-                         (const float*)slab.data_ptr<float>(), blocks, NB, out.data_ptr<float>(),
-                         a.nb, (float*)nullptr);
-    }
+    launch_slab_fwd<binned_fwd_kernel<NB>>(blocks_for(a.n), ReduceFwd{NB, NB, 1, NB, 1, a.nb},
+                                           out.data_ptr<float>(), mu, stream, a);
   });
   return out;
 }
@@ -255,34 +154,19 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> binned_backward(
   TORCH_CHECK(g.numel() == a.nb, "grad_out must have nb elements");
   TORCH_CHECK(!need_w || a.w != nullptr, "weights gradient requested without weights");
   TORCH_CHECK(need_mu || need_sigma || need_w, "no gradient requested");
-  const int nbp = binned_padded(a.nb);
-  torch::Tensor dmu, dsigma, dw;
-  BinnedGrad o;
+  const int nbp = padded_bins(a.nb, "gaussian_binned_sum");
+  BinnedGrad o = {};
   o.g = g.data_ptr<float>();
-  o.dmu = o.dsigma = o.dw = o.slab = nullptr;
-  if (need_mu) {
-    dmu = torch::empty({a.n}, mu.options());
-    o.dmu = dmu.data_ptr<float>();
-  }
-  if (need_sigma) {
-    dsigma = torch::empty({sigma.numel()}, mu.options());
-    o.dsigma = dsigma.data_ptr<float>();
-  }
-  if (need_w) {
-    dw = torch::empty({w->numel()}, mu.options());
-    o.dw = dw.data_ptr<float>();
-  }
-  const bool red_sig = need_sigma && a.sig_b, red_w = need_w && a.w_b;
+  auto dmu = alloc_grad(need_mu, a.n, mu, o.dmu);
+  auto dsigma = alloc_grad(need_sigma, sigma.numel(), mu, o.dsigma);
+  auto dw = alloc_grad(need_w, need_w ? w->numel() : 0, mu, o.dw);
+  const auto r = reduce_sigma_w(a.sig_b ? o.dsigma : nullptr, a.w_b ? o.dw : nullptr);
   auto stream = at::hip::getCurrentHIPStream();
   MG_DISPATCH_BINNED(nbp, {
-    with_bool(need_mu, [&](auto M) {
-      with_bool(need_sigma, [&](auto S) {
-        with_bool(need_w, [&](auto W) {
-          constexpr bool kM = decltype(M)::value, kS = decltype(S)::value, kW = decltype(W)::value;
-          if constexpr (kM || kS || kW)
-            launch_bwd<binned_bwd_kernel<NB, kM, kS, kW>>(a, o, mu, red_sig, red_w, stream);
-        });
-      });
+    with_need3(need_mu, need_sigma, need_w, [&](auto M, auto S, auto W) {
+      launch_slab_bwd<binned_bwd_kernel<NB, decltype(M)::value, decltype(S)::value,
+                                        decltype(W)::value>>(a, o, blocks_for(a.n), 2, r, mu,
+                                                             stream);
     });
   });
   return std::make_tuple(dmu, dsigma, dw);

@@ -29,8 +29,7 @@
 #include <tuple>
 #include <vector>
 
-#include "binned_common.h"
-#include "smf_host.h"
+#include "binned_host.h"
 
 namespace mg {
 
@@ -171,36 +170,6 @@ __global__ __launch_bounds__(kBinThreads) void binned2d_fwd_kernel(Binned2dArgs 
     } else {
       slab[(int64_t)blockIdx.x * (NBX * NBY) + c] = total;
     }
-  }
-}
-
-// Fixed-order sum of the forward slab [rows, ncells] (padded cells, row-major [NBX][nbyp]):
-// workgroup b sums the columns [b * gcols, (b + 1) * gcols) and writes the real cells.
-__global__ __launch_bounds__(kRedThreads) void binned2d_reduce_fwd_kernel(
-    const float* slab, int64_t rows, int ncells, int gcols, int nbyp, int nbx, int nby, float* out) {
-  __shared__ float part[kRedThreads];
-  float t;
-  const int col0 = blockIdx.x * gcols;
-  if (slab_column_sum(slab, rows, ncells, col0, gcols, part, t)) {
-    const int c = col0 + threadIdx.x;
-    const int j = c / nbyp, k = c % nbyp;
-    if (j < nbx && k < nby) out[j * nby + k] = t;
-  }
-}
-
-// The [blocks, 4] slab of broadcast gradients: column c goes to out[c] (null: dropped).
-struct Reduce3 {
-  float* out[4];
-};
-
-__global__ __launch_bounds__(kRedThreads) void binned2d_reduce_bwd_kernel(const float* slab,
-                                                                          int64_t rows, Reduce3 o) {
-  __shared__ float part[kRedThreads];
-  float t;
-  if (slab_column_sum(slab, rows, 4, 0, 4, part, t)) {
-    float* dst = threadIdx.x == 0 ? o.out[0] : threadIdx.x == 1 ? o.out[1] :
-                 threadIdx.x == 2 ? o.out[2] : nullptr;
-    if (dst) dst[0] = t;
   }
 }
 
@@ -384,42 +353,7 @@ __global__ __launch_bounds__(kBinThreads) void binned2d_bwd_kernel(Binned2dArgs 
   }
 }
 
-int padded2d(int nb, const char* axis) {
-  TORCH_CHECK(nb >= 1 && nb <= kMaxBins, "gaussian_binned_sum_2d: 1 <= nb", axis, " <= ", kMaxBins,
-              ", got ", nb);
-  return nb <= 4 ? 4 : nb <= 8 ? 8 : nb <= 16 ? 16 : 32;
-}
-
-#define MG_DISPATCH_PAD(NBP, NAME, ...)                       \
-  switch (NBP) {                                              \
-    case 4: { constexpr int NAME = 4; __VA_ARGS__; break; }   \
-    case 8: { constexpr int NAME = 8; __VA_ARGS__; break; }   \
-    case 16: { constexpr int NAME = 16; __VA_ARGS__; break; } \
-    default: { constexpr int NAME = 32; __VA_ARGS__; break; } \
-  }
-
-// Workgroups that fill the chip once (occupancy x CU count of the device), per kernel.
-template <auto Kernel>
-int64_t chip_blocks2d() {
-  static int64_t cap = resident_blocks(reinterpret_cast<const void*>(Kernel), kBinThreads);
-  return cap;
-}
-
-void set_edges(const std::vector<double>& edges, int nb, float (&dst)[kMaxBins + 1]) {
-  for (int e = 1; e <= nb; ++e)
-    TORCH_CHECK(edges[e] > edges[e - 1],
-                "gaussian_binned_sum_2d: edges must be strictly increasing");
-  for (int e = 0; e <= kMaxBins; ++e) dst[e] = (float)edges[std::min(e, nb)];
-}
-
-const float* operand(const torch::Tensor& t, const char* name, int64_t n, int& bcast, bool& wide) {
-  check_dev(t, name, at::kFloat);
-  TORCH_CHECK(t.numel() == n || t.numel() == 1, name, " must have N elements or one");
-  bcast = t.numel() == 1 && n != 1;
-  const float* p = t.data_ptr<float>();
-  wide = wide && (bcast || aligned_to(p, 16));
-  return p;
-}
+constexpr const char* kOp2d = "gaussian_binned_sum_2d";
 
 Binned2dArgs make_args2d(const torch::Tensor& mux, const torch::Tensor& sigx,
                          const torch::Tensor& muy, const torch::Tensor& sigy,
@@ -429,10 +363,10 @@ Binned2dArgs make_args2d(const torch::Tensor& mux, const torch::Tensor& sigx,
   a.n = mux.numel();
   a.nbx = (int)ex.size() - 1;
   a.nby = (int)ey.size() - 1;
-  padded2d(a.nbx, "x");
-  padded2d(a.nby, "y");
-  set_edges(ex, a.nbx, a.ex);
-  set_edges(ey, a.nby, a.ey);
+  padded_bins(a.nbx, kOp2d, "x");
+  padded_bins(a.nby, kOp2d, "y");
+  set_edges(ex, a.nbx, a.ex, kOp2d);
+  set_edges(ey, a.nby, a.ey, kOp2d);
   bool wide = true;
   int none = 0;
   a.mux = operand(mux, "mu_x", a.n, none, wide);
@@ -454,24 +388,15 @@ torch::Tensor binned2d_forward(torch::Tensor mux, torch::Tensor sigx, torch::Ten
                                std::vector<double> ex, std::vector<double> ey) {
   Binned2dArgs a = make_args2d(mux, sigx, muy, sigy, w, ex, ey);
   TORCH_CHECK(a.n > 0, "binned2d_forward: empty input");
-  const int nbxp = padded2d(a.nbx, "x"), nbyp = padded2d(a.nby, "y");
+  const int nbxp = padded_bins(a.nbx, kOp2d, "x"), nbyp = padded_bins(a.nby, kOp2d, "y");
   auto out = torch::empty({a.nbx, a.nby}, mux.options());
   auto stream = at::hip::getCurrentHIPStream();
   const int64_t tiles = (a.n + kTile - 1) / kTile;
   MG_DISPATCH_PAD(nbxp, NBX, MG_DISPATCH_PAD(nbyp, NBY, {
-    const int64_t blocks = std::min(tiles, chip_blocks2d<binned2d_fwd_kernel<NBX, NBY>>());
-    if (blocks == 1) {
-      hipLaunchKernelGGL((binned2d_fwd_kernel<NBX, NBY>), dim3(1), dim3(kBinThreads), 0, stream, a,
-                         (float*)nullptr, out.data_ptr<float>(), 1);
-    } else {
-      constexpr int kCells = NBX * NBY, kGroup = kCells < 32 ? kCells : 32;
-      auto slab = torch::empty({blocks, (int64_t)kCells}, mux.options());
-      hipLaunchKernelGGL((binned2d_fwd_kernel<NBX, NBY>), dim3(blocks), dim3(kBinThreads), 0,
-                         stream, a, slab.data_ptr<float>(), (float*)nullptr, 0);
-      hipLaunchKernelGGL(binned2d_reduce_fwd_kernel, dim3(kCells / kGroup), dim3(kRedThreads), 0,
-                         stream, (const float*)slab.data_ptr<float>(), blocks, kCells, kGroup, NBY,
-                         a.nbx, a.nby, out.data_ptr<float>());
-    }
+    constexpr int kCells = NBX * NBY, kGroup = kCells < 32 ? kCells : 32;
+    launch_slab_fwd<binned2d_fwd_kernel<NBX, NBY>>(
+        tiles, ReduceFwd{kCells, kGroup, kCells / kGroup, NBY, a.nbx, a.nby},
+        out.data_ptr<float>(), mux, stream, a);
   }));
   return out;
 }
@@ -491,17 +416,11 @@ std::vector<torch::Tensor> binned2d_backward(torch::Tensor mux, torch::Tensor si
   TORCH_CHECK(need.size() == 5, "need: five flags");
   TORCH_CHECK(!need[4] || a.w != nullptr, "weights gradient requested without weights");
   TORCH_CHECK(need[0] || need[1] || need[2] || need[3] || need[4], "no gradient requested");
-  const int nbyp = padded2d(a.nby, "y");
+  const int nbyp = padded_bins(a.nby, kOp2d, "y");
   std::vector<torch::Tensor> grads(5);
   const int64_t sizes[5] = {a.n, sigx.numel(), a.n, sigy.numel(), a.w ? w->numel() : 0};
   float* ptr[5];
-  for (int i = 0; i < 5; ++i) {
-    ptr[i] = nullptr;
-    if (need[i]) {
-      grads[i] = torch::empty({sizes[i]}, mux.options());
-      ptr[i] = grads[i].data_ptr<float>();
-    }
-  }
+  for (int i = 0; i < 5; ++i) grads[i] = alloc_grad(need[i], sizes[i], mux, ptr[i]);
   Binned2dGrad o;
   o.g = g.data_ptr<float>();
   o.dmux = ptr[0];
@@ -512,29 +431,14 @@ std::vector<torch::Tensor> binned2d_backward(torch::Tensor mux, torch::Tensor si
   o.slab = nullptr;
   o.need_x = need[0] || need[1];
   o.need_y = need[2] || need[3];
-  const bool red_sx = need[1] && a.sigx_b, red_sy = need[3] && a.sigy_b, red_w = need[4] && a.w_b;
+  ReduceBwd r = {};  // the [blocks, 4] slab: sigma_x, sigma_y, w, unused
+  r.out[0] = a.sigx_b ? o.dsigx : nullptr;
+  r.out[1] = a.sigy_b ? o.dsigy : nullptr;
+  r.out[2] = a.w_b ? o.dw : nullptr;
   auto stream = at::hip::getCurrentHIPStream();
   MG_DISPATCH_PAD(nbyp, NBY, {
     constexpr int V = NBY == 32 ? 2 : 4;
-    const int64_t want = ((a.n + V - 1) / V + kBinThreads - 1) / kBinThreads;
-    const int64_t blocks = std::min(want, chip_blocks2d<binned2d_bwd_kernel<NBY, V>>());
-    const bool two = (red_sx || red_sy || red_w) && blocks > 1;
-    torch::Tensor slab;
-    if (two) {
-      slab = torch::empty({blocks, 4}, mux.options());
-      o.slab = slab.data_ptr<float>();
-    }
-    hipLaunchKernelGGL((binned2d_bwd_kernel<NBY, V>), dim3(blocks), dim3(kBinThreads), 0, stream,
-                       a, o, blocks == 1 ? 1 : 0);
-    if (two) {
-      Reduce3 r;
-      r.out[0] = red_sx ? o.dsigx : nullptr;
-      r.out[1] = red_sy ? o.dsigy : nullptr;
-      r.out[2] = red_w ? o.dw : nullptr;
-      r.out[3] = nullptr;
-      hipLaunchKernelGGL(binned2d_reduce_bwd_kernel, dim3(1), dim3(kRedThreads), 0, stream,
-                         (const float*)o.slab, blocks, r);
-    }
+    launch_slab_bwd<binned2d_bwd_kernel<NBY, V>>(a, o, blocks_for(a.n, V), 4, r, mux, stream);
   });
   return grads;
 }

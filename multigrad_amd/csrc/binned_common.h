@@ -1,6 +1,8 @@
 // Device helpers shared by the Gaussian-binned-sum ops (binned.hip, binned_hvp.hip,
-// binned2d.hip, binned_multi.hip): the edge CDF, guarded vector loads of per-object operands,
-// the fixed-order slab column sum and the operands of the one-axis op.
+// binned_jvp.hip, binned2d.hip, binned_multi.hip, binned_group.hip, binned_fine.hip,
+// binned_reduce.hip): the edge CDF, guarded vector loads and stores of per-object operands, the
+// fixed-order slab column sum, the operands of the one-axis op, and the gradient outputs and
+// epilogue of the object-parallel backward kernels.
 #pragma once
 #include "common.h"
 #include "smf_device.h"
@@ -159,6 +161,44 @@ __device__ __forceinline__ void load_quad(const BinnedArgs& a, int64_t q, float 
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j) inv[j] = 1.0f / s[j];
+}
+
+// The cotangent and the gradient outputs of an object-parallel backward over quads of objects
+// (binned.hip, binned_group.hip, binned_fine.hip).
+struct BinnedGrad {
+  const float* g;  // the cotangent: [nb], or [G, nb] per group
+  float* dmu;      // [n]
+  float* dsigma;   // [n], or [1] when sigma is broadcast
+  float* dw;       // [n], or [1] when w is broadcast
+  float* slab;     // [blocks, 2] partial sums of the broadcast gradients (col 0 sigma, col 1 w)
+};
+
+// The gradient v of one operand for the quad at i0: a broadcast operand (`reduce`) adds the
+// quad's sum to this thread's share, a per-object one stores the quad to dst.
+__device__ __forceinline__ void put_quad(bool reduce, float& share, float* dst, int64_t i0,
+                                         int64_t n, const float (&v)[4]) {
+  if (reduce) share += (v[0] + v[1]) + (v[2] + v[3]);
+  else store_group<4>(dst, i0, n, v);
+}
+
+// The end of such a kernel: the threads' shares rs of the broadcast gradients (0 sigma, 1 w)
+// are summed over the workgroup (red: 2 floats per wave) and go to the outputs when one
+// workgroup covers the input (`direct`), else to the workgroup's slab row.  red_sig / red_w
+// are uniform over the grid.
+__device__ __forceinline__ void finish_broadcast(float (&rs)[2], float* red, bool red_sig,
+                                                 bool red_w, float* dsigma, float* dw, float* slab,
+                                                 int direct) {
+  if (!red_sig && !red_w) return;
+  block_sum_n<2>(rs, red);
+  if (threadIdx.x == 0) {
+    if (direct) {
+      if (red_sig) dsigma[0] = rs[0];
+      if (red_w) dw[0] = rs[1];
+    } else {
+      slab[(int64_t)blockIdx.x * 2 + 0] = rs[0];
+      slab[(int64_t)blockIdx.x * 2 + 1] = rs[1];
+    }
+  }
 }
 
 }  // namespace mg

@@ -28,8 +28,6 @@
 #include <ATen/hip/HIPContext.h>
 
 #include <cmath>
-#include <map>
-#include <mutex>
 #include <tuple>
 #include <utility>
 
@@ -209,16 +207,8 @@ __global__ __launch_bounds__(kBinThreads) void fine_final_kernel(const unsigned 
   out[k] = meta[1] != 0u ? __uint_as_float(0x7fc00000u) : (float)v;
 }
 
-struct FineBwdArgs {
-  const float* g;  // [nb] cotangent
-  float* dmu;      // [n]
-  float* dsigma;   // [n], or [1] when sigma is broadcast
-  float* dw;       // [n], or [1] when w is broadcast
-  float* slab;     // [blocks, 2] partial sums of the broadcast gradients (col 0 sigma, col 1 w)
-};
-
 template <bool GMU, bool GSIG, bool GW>
-__global__ __launch_bounds__(kBinThreads) void fine_bwd_kernel(FineArgs a, FineBwdArgs o,
+__global__ __launch_bounds__(kBinThreads) void fine_bwd_kernel(FineArgs a, BinnedGrad o,
                                                                int direct) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fine_lds[];
   __shared__ float red[2 * (kBinThreads / kWave)];
@@ -284,93 +274,31 @@ __global__ __launch_bounds__(kBinThreads) void fine_bwd_kernel(FineArgs a, FineB
       dc[j] = C;
     }
     if constexpr (GMU) store_group<4>(o.dmu, i0, a.n, dm);
-    if constexpr (GSIG) {
-      if (red_sig) rs[0] += (ds[0] + ds[1]) + (ds[2] + ds[3]);
-      else store_group<4>(o.dsigma, i0, a.n, ds);
-    }
-    if constexpr (GW) {
-      if (red_w) rs[1] += (dc[0] + dc[1]) + (dc[2] + dc[3]);
-      else store_group<4>(o.dw, i0, a.n, dc);
-    }
+    if constexpr (GSIG) put_quad(red_sig, rs[0], o.dsigma, i0, a.n, ds);
+    if constexpr (GW) put_quad(red_w, rs[1], o.dw, i0, a.n, dc);
   }
-  if (red_sig || red_w) {  // uniform over the grid
-    block_sum_n<2>(rs, red);
-    if (threadIdx.x == 0) {
-      if (direct) {
-        if (red_sig) o.dsigma[0] = rs[0];
-        if (red_w) o.dw[0] = rs[1];
-      } else {
-        o.slab[(int64_t)blockIdx.x * 2 + 0] = rs[0];
-        o.slab[(int64_t)blockIdx.x * 2 + 1] = rs[1];
-      }
-    }
-  }
-}
-
-// Workgroups of `kernel` that fill the chip once with `lds` bytes of dynamic LDS each; the query
-// costs ~20 us of host time, so the answer is kept per kernel and LDS size.
-int64_t fine_blocks(const void* kernel, size_t lds) {
-  static std::mutex mu;
-  static std::map<std::pair<const void*, size_t>, int64_t> cache;
-  std::lock_guard<std::mutex> lock(mu);
-  const auto key = std::make_pair(kernel, lds);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  int dev = 0, occ = 0;
-  (void)hipGetDevice(&dev);
-  hipDeviceProp_t prop;
-  (void)hipGetDeviceProperties(&prop, dev);
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, kBinThreads, lds);
-  const int64_t cap = (int64_t)std::max(1, occ) * prop.multiProcessorCount;
-  cache[key] = cap;
-  return cap;
+  finish_broadcast(rs, red, red_sig, red_w, o.dsigma, o.dw, o.slab, direct);
 }
 
 FineArgs make_fine_args(const torch::Tensor& mu, const torch::Tensor& sigma,
                         const c10::optional<torch::Tensor>& w, const torch::Tensor& edges) {
-  check_dev(mu, "mu", at::kFloat);
-  check_dev(sigma, "sigma", at::kFloat);
-  check_dev(edges, "edges", at::kFloat);
   FineArgs a;
   a.n = mu.numel();
+  bool wide = true;
+  int none = 0;
+  a.mu = operand(mu, "mu", a.n, none, wide);
+  a.sigma = operand(sigma, "sigma", a.n, a.sig_b, wide);
+  check_dev(edges, "edges", at::kFloat);
   a.nb = (int)edges.numel() - 1;
   TORCH_CHECK(edges.numel() >= 2 && a.nb <= kFineMaxBins, "gaussian_binned_sum_fine: 1 <= nb <= ",
               kFineMaxBins, ", got ", edges.numel() - 1);
   TORCH_CHECK(a.n > 0 && a.n < (int64_t(1) << 31), "gaussian_binned_sum_fine: 0 < N < 2^31 required");
-  TORCH_CHECK(sigma.numel() == a.n || sigma.numel() == 1, "sigma must have N elements or one");
-  a.mu = mu.data_ptr<float>();
-  a.sigma = sigma.data_ptr<float>();
   a.edge = edges.data_ptr<float>();
-  a.sig_b = sigma.numel() == 1 && a.n != 1;
   a.w = nullptr;
   a.w_b = 0;
-  if (w.has_value() && w->defined()) {
-    check_dev(*w, "weights", at::kFloat);
-    TORCH_CHECK(w->numel() == a.n || w->numel() == 1, "weights must have N elements or one");
-    a.w = w->data_ptr<float>();
-    a.w_b = w->numel() == 1 && a.n != 1;
-  }
-  a.vec = aligned16(a.mu) && (a.sig_b || aligned16(a.sigma)) &&
-          (a.w == nullptr || a.w_b || aligned16(a.w));
+  if (w.has_value() && w->defined()) a.w = operand(*w, "weights", a.n, a.w_b, wide);
+  a.vec = wide;
   return a;
-}
-
-template <auto Kernel>
-void launch_fine_bwd(const FineArgs& a, FineBwdArgs& o, const torch::Tensor& like, bool red_sig,
-                     bool red_w, hipStream_t stream) {
-  const size_t lds = (size_t)(2 * a.nb + 1) * sizeof(float);
-  const int64_t need = ((a.n + 3) / 4 + kBinThreads - 1) / kBinThreads;
-  const int64_t blocks = std::min(need, fine_blocks(reinterpret_cast<const void*>(Kernel), lds));
-  const bool two = (red_sig || red_w) && blocks > 1;
-  torch::Tensor slab;
-  if (two) {
-    slab = torch::empty({blocks, 2}, like.options());
-    o.slab = slab.data_ptr<float>();
-  }
-  hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(kBinThreads), lds, stream, a, o, blocks == 1 ? 1 : 0);
-  if (two)
-    launch_binned_reduce(o.slab, blocks, 2, red_sig ? o.dsigma : nullptr, 1,
-                         red_w ? o.dw : nullptr, stream);
 }
 
 }  // namespace
@@ -386,19 +314,19 @@ torch::Tensor binned_fine_forward(torch::Tensor mu, torch::Tensor sigma,
   auto out = torch::empty({(int64_t)a.nb}, mu.options());
   auto* accp = reinterpret_cast<unsigned long long*>(acc.data_ptr<int64_t>());
   const size_t lds = (size_t)a.nb * 8 + (size_t)(a.nb + 1) * sizeof(float);
-  const int64_t need = ((a.n + 3) / 4 + kBinThreads - 1) / kBinThreads;
+  const int64_t need = blocks_for(a.n);
   if (perw) {
     const int64_t mblocks = std::min(need, chip_blocks<fine_maxabs_kernel>());
     hipLaunchKernelGGL(fine_maxabs_kernel, dim3(mblocks), dim3(kBinThreads), 0, stream, a.w, a.n,
                        aligned16(a.w) ? 1 : 0, accp, a.nb);
     const int64_t blocks =
-        std::min(need, fine_blocks(reinterpret_cast<const void*>(fine_fwd_kernel<true>), lds));
+        std::min(need, chip_blocks(reinterpret_cast<const void*>(fine_fwd_kernel<true>), lds));
     hipLaunchKernelGGL(fine_fwd_kernel<true>, dim3(blocks), dim3(kBinThreads), lds, stream, a, accp);
   } else {
     a.w = nullptr;
     a.w_b = 0;
     const int64_t blocks =
-        std::min(need, fine_blocks(reinterpret_cast<const void*>(fine_fwd_kernel<false>), lds));
+        std::min(need, chip_blocks(reinterpret_cast<const void*>(fine_fwd_kernel<false>), lds));
     hipLaunchKernelGGL(fine_fwd_kernel<false>, dim3(blocks), dim3(kBinThreads), lds, stream, a,
                        accp);
   }
@@ -418,32 +346,17 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> binned_fine_backward(
   TORCH_CHECK(g.numel() == a.nb, "grad_out must have nb elements");
   TORCH_CHECK(!need_w || a.w != nullptr, "weights gradient requested without weights");
   TORCH_CHECK(need_mu || need_sigma || need_w, "no gradient requested");
-  torch::Tensor dmu, dsigma, dw;
-  FineBwdArgs o;
+  BinnedGrad o = {};
   o.g = g.data_ptr<float>();
-  o.dmu = o.dsigma = o.dw = o.slab = nullptr;
-  if (need_mu) {
-    dmu = torch::empty({a.n}, mu.options());
-    o.dmu = dmu.data_ptr<float>();
-  }
-  if (need_sigma) {
-    dsigma = torch::empty({sigma.numel()}, mu.options());
-    o.dsigma = dsigma.data_ptr<float>();
-  }
-  if (need_w) {
-    dw = torch::empty({w->numel()}, mu.options());
-    o.dw = dw.data_ptr<float>();
-  }
-  const bool red_sig = need_sigma && a.sig_b, red_w = need_w && a.w_b;
+  auto dmu = alloc_grad(need_mu, a.n, mu, o.dmu);
+  auto dsigma = alloc_grad(need_sigma, sigma.numel(), mu, o.dsigma);
+  auto dw = alloc_grad(need_w, need_w ? w->numel() : 0, mu, o.dw);
+  const auto r = reduce_sigma_w(a.sig_b ? o.dsigma : nullptr, a.w_b ? o.dw : nullptr);
+  const size_t lds = (size_t)(2 * a.nb + 1) * sizeof(float);  // the cotangent and the edges
   auto stream = at::hip::getCurrentHIPStream();
-  with_bool(need_mu, [&](auto M) {
-    with_bool(need_sigma, [&](auto S) {
-      with_bool(need_w, [&](auto W) {
-        constexpr bool kM = decltype(M)::value, kS = decltype(S)::value, kW = decltype(W)::value;
-        if constexpr (kM || kS || kW)
-          launch_fine_bwd<fine_bwd_kernel<kM, kS, kW>>(a, o, mu, red_sig, red_w, stream);
-      });
-    });
+  with_need3(need_mu, need_sigma, need_w, [&](auto M, auto S, auto W) {
+    launch_slab_bwd<fine_bwd_kernel<decltype(M)::value, decltype(S)::value, decltype(W)::value>>(
+        a, o, blocks_for(a.n), 2, r, mu, stream, lds);
   });
   return std::make_tuple(dmu, dsigma, dw);
 }

@@ -277,19 +277,14 @@ __global__ __launch_bounds__(kGbThreads) void binned_group_fwd_kernel(GroupFwdAr
   }
 }
 
-struct GroupBwdArgs {
-  const int* id;   // [n] group of every object, each in [0, G)
-  const float* g;  // [G, nb] cotangent
-  float* dmu;      // [n]
-  float* dsigma;   // [n], or [1] when sigma is broadcast
-  float* dw;       // [n], or [1] when w is broadcast
-  float* slab;     // [blocks, 2] partial sums of the broadcast gradients (col 0 sigma, col 1 w)
+// g is the [G, nb] table of cotangent rows; id[i] in [0, G) is the row of object i.
+struct GroupGrad : BinnedGrad {
+  const int* id;  // [n]
 };
 
 template <int NB, bool GMU, bool GSIG, bool GW>
 __global__ __launch_bounds__(kBinThreads) void binned_group_bwd_kernel(BinnedArgs a,
-                                                                       GroupBwdArgs o,
-                                                                       int direct) {
+                                                                       GroupGrad o, int direct) {
   __shared__ float red[2 * (kBinThreads / kWave)];
   const bool red_sig = GSIG && a.sig_b, red_w = GW && a.w_b;
   float rs[2] = {0.0f, 0.0f};  // this thread's share of the broadcast gradients
@@ -349,6 +344,10 @@ __global__ __launch_bounds__(kBinThreads) void binned_group_bwd_kernel(BinnedArg
       if (i0 + j >= a.n) C[j] = 0.0f;
     }
     if constexpr (GMU) store_group<4>(o.dmu, i0, a.n, dm);
+    // put_quad and finish_broadcast (binned_common.h), written out: this kernel is close to
+    // its register limits, and through the helpers (the same operations, blocks laid out in
+    // another order) its instances are allocated up to 4 more VGPRs; NB = 16 with all three
+    // gradients goes from 72 to 74 and loses a wave, and with it the grid and the sum order.
     if constexpr (GSIG) {
       if (red_sig) rs[0] += (ds[0] + ds[1]) + (ds[2] + ds[3]);
       else store_group<4>(o.dsigma, i0, a.n, ds);
@@ -370,23 +369,6 @@ __global__ __launch_bounds__(kBinThreads) void binned_group_bwd_kernel(BinnedArg
       }
     }
   }
-}
-
-template <auto Kernel>
-void launch_group_bwd(const BinnedArgs& a, GroupBwdArgs& o, const torch::Tensor& like,
-                      bool red_sig, bool red_w, hipStream_t stream) {
-  const int64_t need = ((a.n + 3) / 4 + kBinThreads - 1) / kBinThreads;
-  const int64_t blocks = std::min(need, chip_blocks<Kernel>());
-  const bool two = (red_sig || red_w) && blocks > 1;
-  torch::Tensor slab;
-  if (two) {
-    slab = torch::empty({blocks, 2}, like.options());
-    o.slab = slab.data_ptr<float>();
-  }
-  hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(kBinThreads), 0, stream, a, o, blocks == 1 ? 1 : 0);
-  if (two)
-    launch_binned_reduce(o.slab, blocks, 2, red_sig ? o.dsigma : nullptr, 1,
-                         red_w ? o.dw : nullptr, stream);
 }
 
 void check_plan(const torch::Tensor& ids, int64_t n, int64_t num_groups, const char* what) {
@@ -477,36 +459,20 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> binned_group_backward(
   TORCH_CHECK(!need_w || a.w != nullptr, "weights gradient requested without weights");
   TORCH_CHECK(need_mu || need_sigma || need_w, "no gradient requested");
   a.vec = a.vec && aligned16(ids.data_ptr<int>());
-  const int nbp = binned_padded(a.nb);
-  torch::Tensor dmu, dsigma, dw;
-  GroupBwdArgs o;
+  const int nbp = padded_bins(a.nb, "gaussian_binned_sum");
+  GroupGrad o = {};
   o.id = ids.data_ptr<int>();
   o.g = g.data_ptr<float>();
-  o.dmu = o.dsigma = o.dw = o.slab = nullptr;
-  if (need_mu) {
-    dmu = torch::empty({a.n}, mu.options());
-    o.dmu = dmu.data_ptr<float>();
-  }
-  if (need_sigma) {
-    dsigma = torch::empty({sigma.numel()}, mu.options());
-    o.dsigma = dsigma.data_ptr<float>();
-  }
-  if (need_w) {
-    dw = torch::empty({w->numel()}, mu.options());
-    o.dw = dw.data_ptr<float>();
-  }
-  const bool red_sig = need_sigma && a.sig_b, red_w = need_w && a.w_b;
+  auto dmu = alloc_grad(need_mu, a.n, mu, o.dmu);
+  auto dsigma = alloc_grad(need_sigma, sigma.numel(), mu, o.dsigma);
+  auto dw = alloc_grad(need_w, need_w ? w->numel() : 0, mu, o.dw);
+  const auto r = reduce_sigma_w(a.sig_b ? o.dsigma : nullptr, a.w_b ? o.dw : nullptr);
   auto stream = at::hip::getCurrentHIPStream();
   MG_DISPATCH_BINNED(nbp, {
-    with_bool(need_mu, [&](auto M) {
-      with_bool(need_sigma, [&](auto S) {
-        with_bool(need_w, [&](auto W) {
-          constexpr bool kM = decltype(M)::value, kS = decltype(S)::value, kW = decltype(W)::value;
-          if constexpr (kM || kS || kW)
-            launch_group_bwd<binned_group_bwd_kernel<NB, kM, kS, kW>>(a, o, mu, red_sig, red_w,
-                                                                      stream);
-        });
-      });
+    with_need3(need_mu, need_sigma, need_w, [&](auto M, auto S, auto W) {
+      launch_slab_bwd<binned_group_bwd_kernel<NB, decltype(M)::value, decltype(S)::value,
+                                              decltype(W)::value>>(a, o, blocks_for(a.n), 2, r,
+                                                                   mu, stream);
     });
   });
   return std::make_tuple(dmu, dsigma, dw);

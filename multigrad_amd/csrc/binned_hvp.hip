@@ -141,27 +141,10 @@ __global__ __launch_bounds__(kBinThreads) void binned_bwd2_kernel(BinnedArgs a, 
       gw[j] = -r * (ca[j] * M0[j] + cb[j] * M1[j]);
     }
     if (o.gmu != nullptr) store_group<4>(o.gmu, i0, a.n, gm);
-    if (o.gsigma != nullptr) {
-      if (red_sig) rs[0] += (gs[0] + gs[1]) + (gs[2] + gs[3]);
-      else store_group<4>(o.gsigma, i0, a.n, gs);
-    }
-    if (o.gw != nullptr) {
-      if (red_w) rs[1] += (gw[0] + gw[1]) + (gw[2] + gw[3]);
-      else store_group<4>(o.gw, i0, a.n, gw);
-    }
+    if (o.gsigma != nullptr) put_quad(red_sig, rs[0], o.gsigma, i0, a.n, gs);
+    if (o.gw != nullptr) put_quad(red_w, rs[1], o.gw, i0, a.n, gw);
   }
-  if (red_sig || red_w) {  // uniform over the grid
-    block_sum_n<2>(rs, red);
-    if (threadIdx.x == 0) {
-      if (direct) {
-        if (red_sig) o.gsigma[0] = rs[0];
-        if (red_w) o.gw[0] = rs[1];
-      } else {
-        o.slab_b[(int64_t)blockIdx.x * 2 + 0] = rs[0];
-        o.slab_b[(int64_t)blockIdx.x * 2 + 1] = rs[1];
-      }
-    }
-  }
+  finish_broadcast(rs, red, red_sig, red_w, o.gsigma, o.gw, o.slab_b, direct);
   if constexpr (GG) {
     __syncthreads();  // `red` may still be read by thread 0 of the sum above
     block_sum_n<NB>(acc, red);
@@ -181,8 +164,7 @@ __global__ __launch_bounds__(kBinThreads) void binned_bwd2_kernel(BinnedArgs a, 
 template <auto Kernel, int NB, bool GG>
 void launch_bwd2(const BinnedArgs& a, Binned2& o, const torch::Tensor& like, bool red_b,
                  hipStream_t stream) {
-  const int64_t need = ((a.n + 3) / 4 + kBinThreads - 1) / kBinThreads;
-  const int64_t blocks = std::min(need, chip_blocks<Kernel>());
+  const int64_t blocks = std::min(blocks_for(a.n), chip_blocks<Kernel>());
   const bool two = blocks > 1;
   torch::Tensor slab_b, slab_g;
   if (two && red_b) {
@@ -195,17 +177,10 @@ void launch_bwd2(const BinnedArgs& a, Binned2& o, const torch::Tensor& like, boo
   }
   hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(kBinThreads), 0, stream, a, o, two ? 0 : 1);
   if (two && red_b)
-    launch_binned_reduce(o.slab_b, blocks, 2, a.sig_b ? o.gsigma : nullptr, 1,
-                         a.w_b ? o.gw : nullptr, stream);
-  if (two && GG) launch_binned_reduce(o.slab_g, blocks, NB, o.gg, a.nb, nullptr, stream);
-}
-
-// The pointer of an optional cotangent with `numel` elements (nullptr: absent, a zero).
-const float* cotangent(const c10::optional<torch::Tensor>& t, const char* name, int64_t numel) {
-  if (!t.has_value() || !t->defined()) return nullptr;
-  check_dev(*t, name, at::kFloat);
-  TORCH_CHECK(t->numel() == numel, name, " has ", t->numel(), " elements, expected ", numel);
-  return t->data_ptr<float>();
+    launch_reduce_bwd(o.slab_b, blocks, 2,
+                      reduce_sigma_w(a.sig_b ? o.gsigma : nullptr, a.w_b ? o.gw : nullptr), stream);
+  if (two && GG)
+    launch_reduce_fwd(o.slab_g, blocks, ReduceFwd{NB, NB, 1, NB, 1, a.nb}, o.gg, stream);
 }
 
 }  // namespace
@@ -224,36 +199,22 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> binned_ba
   TORCH_CHECK(g.numel() == a.nb, "grad_out must have nb elements");
   TORCH_CHECK(!need_w || a.w != nullptr, "weights gradient requested without weights");
   TORCH_CHECK(need_mu || need_sigma || need_w || need_g, "no gradient requested");
-  Binned2 o;
+  Binned2 o = {};
   o.g = g.data_ptr<float>();
-  o.a = cotangent(ca, "the cotangent of dmu", a.n);
-  o.b = cotangent(cb, "the cotangent of dsigma", sigma.numel());
-  o.c = cotangent(cc, "the cotangent of dw", a.w != nullptr ? w->numel() : 0);
+  o.a = optional_operand(ca, "the cotangent of dmu", a.n);
+  o.b = optional_operand(cb, "the cotangent of dsigma", sigma.numel());
+  o.c = optional_operand(cc, "the cotangent of dw", a.w != nullptr ? w->numel() : 0);
   TORCH_CHECK(o.a != nullptr || o.b != nullptr || o.c != nullptr, "no cotangent given");
   a.vec = a.vec && (o.a == nullptr || aligned16(o.a)) &&
           (o.b == nullptr || a.sig_b || aligned16(o.b)) &&
           (o.c == nullptr || a.w_b || aligned16(o.c));
-  o.gmu = o.gsigma = o.gw = o.gg = o.slab_b = o.slab_g = nullptr;
-  torch::Tensor gmu, gsigma, gw, gg;
-  if (need_mu) {
-    gmu = torch::empty({a.n}, mu.options());
-    o.gmu = gmu.data_ptr<float>();
-  }
-  if (need_sigma) {
-    gsigma = torch::empty({sigma.numel()}, mu.options());
-    o.gsigma = gsigma.data_ptr<float>();
-  }
-  if (need_w) {
-    gw = torch::empty({w->numel()}, mu.options());
-    o.gw = gw.data_ptr<float>();
-  }
-  if (need_g) {
-    gg = torch::empty({a.nb}, mu.options());
-    o.gg = gg.data_ptr<float>();
-  }
+  auto gmu = alloc_grad(need_mu, a.n, mu, o.gmu);
+  auto gsigma = alloc_grad(need_sigma, sigma.numel(), mu, o.gsigma);
+  auto gw = alloc_grad(need_w, need_w ? w->numel() : 0, mu, o.gw);
+  auto gg = alloc_grad(need_g, a.nb, mu, o.gg);
   const bool cdf = need_g && o.c != nullptr;
   const bool red_b = (need_sigma && a.sig_b) || (need_w && a.w_b);
-  const int nbp = binned_padded(a.nb);
+  const int nbp = padded_bins(a.nb, "gaussian_binned_sum");
   auto stream = at::hip::getCurrentHIPStream();
   MG_DISPATCH_BINNED(nbp, {
     with_bool(need_g, [&](auto G) {

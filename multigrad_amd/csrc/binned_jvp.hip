@@ -108,26 +108,8 @@ __global__ __launch_bounds__(kBinThreads) void binned_jvp_kernel(BinnedArgs a, B
 template <int NB, bool TW>
 void launch_jvp(const BinnedArgs& a, const BinnedTangent& t, torch::Tensor& out,
                 hipStream_t stream) {
-  const int64_t need = ((a.n + 3) / 4 + kBinThreads - 1) / kBinThreads;
-  const int64_t blocks = std::min(need, chip_blocks<binned_jvp_kernel<NB, TW>>());
-  if (blocks == 1) {
-    hipLaunchKernelGGL((binned_jvp_kernel<NB, TW>), dim3(1), dim3(kBinThreads), 0, stream, a, t,
-                       (float*)nullptr, out.data_ptr<float>(), 1);
-  } else {
-    auto slab = torch::empty({blocks, (int64_t)NB}, out.options());
-    hipLaunchKernelGGL((binned_jvp_kernel<NB, TW>), dim3(blocks), dim3(kBinThreads), 0, stream, a,
-                       t, slab.data_ptr<float>(), (float*)nullptr, 0);
-    launch_binned_reduce(slab.data_ptr<float>(), blocks, NB, out.data_ptr<float>(), a.nb, nullptr,
-                         stream);
-  }
-}
-
-// The pointer of an optional tangent with `numel` elements (nullptr: absent, a zero).
-const float* tangent(const c10::optional<torch::Tensor>& t, const char* name, int64_t numel) {
-  if (!t.has_value() || !t->defined()) return nullptr;
-  check_dev(*t, name, at::kFloat);
-  TORCH_CHECK(t->numel() == numel, name, " has ", t->numel(), " elements, expected ", numel);
-  return t->data_ptr<float>();
+  launch_slab_fwd<binned_jvp_kernel<NB, TW>>(blocks_for(a.n), ReduceFwd{NB, NB, 1, NB, 1, a.nb},
+                                             out.data_ptr<float>(), out, stream, a, t);
 }
 
 }  // namespace
@@ -140,11 +122,11 @@ torch::Tensor binned_jvp(torch::Tensor mu, torch::Tensor sigma, c10::optional<to
   BinnedArgs a = make_args(mu, sigma, w, edges);
   TORCH_CHECK(a.n > 0, "binned_jvp: empty input");
   BinnedTangent t;
-  t.tmu = tangent(tmu, "the tangent of mu", a.n);
-  t.tsigma = tangent(tsigma, "the tangent of sigma", sigma.numel());
+  t.tmu = optional_operand(tmu, "the tangent of mu", a.n);
+  t.tsigma = optional_operand(tsigma, "the tangent of sigma", sigma.numel());
   TORCH_CHECK(a.w != nullptr || !tw.has_value() || !tw->defined(),
               "binned_jvp: a weights tangent without weights");
-  t.tw = tangent(tw, "the tangent of the weights", a.w != nullptr ? w->numel() : 0);
+  t.tw = optional_operand(tw, "the tangent of the weights", a.w != nullptr ? w->numel() : 0);
   TORCH_CHECK(t.tmu != nullptr || t.tsigma != nullptr || t.tw != nullptr, "no tangent given");
   if (t.tmu == nullptr && t.tsigma == nullptr)  // linear in w: the forward with tw as weights
     return binned_forward(mu, sigma, *tw, edges);
@@ -152,7 +134,7 @@ torch::Tensor binned_jvp(torch::Tensor mu, torch::Tensor sigma, c10::optional<to
           (t.tsigma == nullptr || a.sig_b || aligned16(t.tsigma)) &&
           (t.tw == nullptr || a.w_b || aligned16(t.tw));
   auto out = torch::empty({a.nb}, mu.options());
-  const int nbp = binned_padded(a.nb);
+  const int nbp = padded_bins(a.nb, "gaussian_binned_sum");
   auto stream = at::hip::getCurrentHIPStream();
   MG_DISPATCH_BINNED(nbp, {
     if (t.tw != nullptr) launch_jvp<NB, true>(a, t, out, stream);

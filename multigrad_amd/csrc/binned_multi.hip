@@ -26,8 +26,7 @@
 
 #include <vector>
 
-#include "binned_common.h"
-#include "smf_host.h"
+#include "binned_host.h"
 
 namespace mg {
 
@@ -123,39 +122,6 @@ __global__ __launch_bounds__(kBinThreads) void binned_multi_fwd_kernel(MultiArgs
     } else {
 #pragma unroll
       for (int k = 0; k < CB * NB; ++k) slab[(int64_t)blockIdx.x * (CB * NB) + k] = acc[k];
-    }
-  }
-}
-
-// Fixed-order sum of the forward slab [rows, ld]: workgroup c sums the nbp columns of channel
-// c (slab_column_sum) and writes its real bins to out[c][0..nb).
-__global__ __launch_bounds__(kRedThreads) void binned_multi_reduce_fwd_kernel(
-    const float* slab, int64_t rows, int ld, int nbp, int nb, float* out) {
-  __shared__ float part[kRedThreads];
-  float t;
-  if (slab_column_sum(slab, rows, ld, blockIdx.x * nbp, nbp, part, t)) {
-    const int k = threadIdx.x;
-    if (k < nb) out[blockIdx.x * nb + k] = t;
-  }
-}
-
-// The [blocks, kRedCols] slab of broadcast gradients: column k goes to out[k] (null: dropped);
-// with `add0`, column 0 (sigma) is added to what an earlier pass left there.
-struct MultiRed {
-  float* out[kRedCols];
-  int add0;
-};
-
-__global__ __launch_bounds__(kRedThreads) void binned_multi_reduce_bwd_kernel(const float* slab,
-                                                                              int64_t rows,
-                                                                              MultiRed r) {
-  __shared__ float part[kRedThreads];
-  float t;
-  if (slab_column_sum(slab, rows, kRedCols, 0, kRedCols, part, t)) {
-#pragma unroll
-    for (int k = 0; k < kRedCols; ++k) {
-      if ((int)threadIdx.x == k && r.out[k] != nullptr)
-        r.out[k][0] = k == 0 && r.add0 ? r.out[k][0] + t : t;
     }
   }
 }
@@ -316,11 +282,7 @@ __global__ __launch_bounds__(kBinThreads) void binned_multi_bwd_kernel(MultiArgs
   }
 }
 
-int multi_padded(int nb) {
-  TORCH_CHECK(nb >= 1 && nb <= kMaxBins, "gaussian_binned_sum_multi: 1 <= nb <= ", kMaxBins,
-              ", got ", nb);
-  return nb <= 4 ? 4 : nb <= 8 ? 8 : nb <= 16 ? 16 : 32;
-}
+constexpr const char* kOpMulti = "gaussian_binned_sum_multi";
 
 #define MG_DISPATCH_MULTI(NBP, NC, ...)                                         \
   switch ((NBP) * 2 + ((NC) > 2 ? 1 : 0)) {                                     \
@@ -334,86 +296,50 @@ int multi_padded(int nb) {
     default: { constexpr int NB = 32, CB = 4; __VA_ARGS__; break; }             \
   }
 
-// Workgroups that fill the chip once (occupancy x CU count of the device), per kernel.
-template <auto Kernel>
-int64_t chip_blocks_multi() {
-  static int64_t cap = resident_blocks(reinterpret_cast<const void*>(Kernel), kBinThreads);
-  return cap;
-}
-
 using Weights = std::vector<c10::optional<torch::Tensor>>;
 
-// The operands shared by every pass; the channels are filled in by set_channels.
+// The operands shared by every pass (vec: mu and sigma are wide); with_channels adds a pass's
+// weights.
 MultiArgs make_multi_args(const torch::Tensor& mu, const torch::Tensor& sigma,
                           const Weights& w, const std::vector<double>& edges) {
-  check_dev(mu, "mu", at::kFloat);
-  check_dev(sigma, "sigma", at::kFloat);
   const int64_t C = (int64_t)w.size();
-  TORCH_CHECK(C >= 1 && C <= kMaxChannels, "gaussian_binned_sum_multi: 1 <= C <= ", kMaxChannels,
-              " weight channels, got ", C);
   MultiArgs a;
   a.n = mu.numel();
   a.nb = (int)edges.size() - 1;
-  multi_padded(a.nb);
-  for (int e = 1; e <= a.nb; ++e)
-    TORCH_CHECK(edges[e] > edges[e - 1],
-                "gaussian_binned_sum_multi: edges must be strictly increasing");
-  for (int e = 0; e <= kMaxBins; ++e) a.edge[e] = (float)edges[std::min(e, a.nb)];
-  TORCH_CHECK(sigma.numel() == a.n || sigma.numel() == 1, "sigma must have N elements or one");
-  a.mu = mu.data_ptr<float>();
-  a.sigma = sigma.data_ptr<float>();
-  a.sig_b = sigma.numel() == 1 && a.n != 1;
+  bool wide = true;
+  int none = 0;
+  a.mu = operand(mu, "mu", a.n, none, wide);
+  a.sigma = operand(sigma, "sigma", a.n, a.sig_b, wide);
+  a.vec = wide;
+  TORCH_CHECK(C >= 1 && C <= kMaxChannels, kOpMulti, ": 1 <= C <= ", kMaxChannels,
+              " weight channels, got ", C);
+  padded_bins(a.nb, kOpMulti);
+  set_edges(edges, a.nb, a.edge, kOpMulti);
   for (const auto& t : w) {
     if (t.has_value() && t->defined()) {
       check_dev(*t, "weights", at::kFloat);
-      TORCH_CHECK(t->numel() == a.n || t->numel() == 1,
-                  "every weights entry must have N elements or one");
+      operand(*t, "every weights entry", a.n, none, wide);
     }
   }
   return a;
 }
 
-// Channels [c0, c0 + nc) of `w` into the pass arguments.
-void set_channels(MultiArgs& a, const Weights& w, int c0, int nc) {
+// The arguments of the pass over channels [c0, c0 + nc) of `w` (checked by make_multi_args).
+MultiArgs with_channels(MultiArgs a, const Weights& w, int c0, int nc) {
   a.nc = nc;
   a.w_b = 0;
-  bool vec = aligned_to(a.mu, 16) && (a.sig_b || aligned_to(a.sigma, 16));
+  bool wide = a.vec;
   for (int c = 0; c < kChanBlock; ++c) {
     a.w[c] = nullptr;
     if (c >= nc) continue;
     const auto& t = w[c0 + c];
     if (!t.has_value() || !t->defined()) continue;
-    a.w[c] = t->data_ptr<float>();
-    if (t->numel() == 1 && a.n != 1) a.w_b |= 1 << c;
-    else vec = vec && aligned_to(a.w[c], 16);
+    int b = 0;
+    a.w[c] = operand(*t, "every weights entry", a.n, b, wide);
+    a.w_b |= b << c;
   }
-  a.vec = vec;
-}
-
-template <auto Kernel>
-void launch_multi_bwd(const MultiArgs& a, MultiGrad& o, const torch::Tensor& like, bool red_sig,
-                      hipStream_t stream) {
-  const int64_t need = ((a.n + 3) / 4 + kBinThreads - 1) / kBinThreads;
-  const int64_t blocks = std::min(need, chip_blocks_multi<Kernel>());
-  MultiRed r;
-  r.add0 = o.accum;
-  bool any = red_sig;
-  r.out[0] = red_sig ? o.dsigma : nullptr;
-  for (int k = 1; k < kRedCols; ++k) {
-    const int c = k - 1;
-    r.out[k] = c < kChanBlock && ((a.w_b >> c) & 1) ? o.dw[c] : nullptr;
-    any = any || r.out[k] != nullptr;
-  }
-  const bool two = any && blocks > 1;
-  torch::Tensor slab;
-  if (two) {
-    slab = torch::empty({blocks, (int64_t)kRedCols}, like.options());
-    o.slab = slab.data_ptr<float>();
-  }
-  hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(kBinThreads), 0, stream, a, o, blocks == 1 ? 1 : 0);
-  if (two)
-    hipLaunchKernelGGL(binned_multi_reduce_bwd_kernel, dim3(1), dim3(kRedThreads), 0, stream,
-                       (const float*)o.slab, blocks, r);
+  a.vec = wide;
+  return a;
 }
 
 }  // namespace
@@ -421,30 +347,19 @@ void launch_multi_bwd(const MultiArgs& a, MultiGrad& o, const torch::Tensor& lik
 // out[C, nb]; weights[c] undefined / None stands for the constant 1.
 torch::Tensor binned_multi_forward(torch::Tensor mu, torch::Tensor sigma, Weights weights,
                                    std::vector<double> edges) {
-  MultiArgs a = make_multi_args(mu, sigma, weights, edges);
-  TORCH_CHECK(a.n > 0, "binned_multi_forward: empty input");
+  const MultiArgs base = make_multi_args(mu, sigma, weights, edges);
+  TORCH_CHECK(base.n > 0, "binned_multi_forward: empty input");
   const int C = (int)weights.size();
-  const int nbp = multi_padded(a.nb);
-  auto out = torch::empty({(int64_t)C, (int64_t)a.nb}, mu.options());
+  const int nb = base.nb, nbp = padded_bins(nb, kOpMulti);
+  auto out = torch::empty({(int64_t)C, (int64_t)nb}, mu.options());
   auto stream = at::hip::getCurrentHIPStream();
-  const int64_t need = ((a.n + 3) / 4 + kBinThreads - 1) / kBinThreads;
   for (int c0 = 0; c0 < C; c0 += kChanBlock) {
     const int nc = std::min(kChanBlock, C - c0);
-    set_channels(a, weights, c0, nc);
-    float* dst = out.data_ptr<float>() + (int64_t)c0 * a.nb;
+    const MultiArgs a = with_channels(base, weights, c0, nc);
     MG_DISPATCH_MULTI(nbp, nc, {
-      const int64_t blocks =
-          std::min(need, chip_blocks_multi<binned_multi_fwd_kernel<NB, CB>>());
-      if (blocks == 1) {
-        hipLaunchKernelGGL((binned_multi_fwd_kernel<NB, CB>), dim3(1), dim3(kBinThreads), 0,
-                           stream, a, (float*)nullptr, dst, 1);
-      } else {
-        auto slab = torch::empty({blocks, (int64_t)(CB * NB)}, mu.options());
-        hipLaunchKernelGGL((binned_multi_fwd_kernel<NB, CB>), dim3(blocks), dim3(kBinThreads), 0,
-                           stream, a, slab.data_ptr<float>(), (float*)nullptr, 0);
-        hipLaunchKernelGGL(binned_multi_reduce_fwd_kernel, dim3(nc), dim3(kRedThreads), 0, stream,
-                           (const float*)slab.data_ptr<float>(), blocks, CB * NB, NB, a.nb, dst);
-      }
+      launch_slab_fwd<binned_multi_fwd_kernel<NB, CB>>(
+          blocks_for(a.n), ReduceFwd{CB * NB, NB, nc, NB, nc, nb},
+          out.data_ptr<float>() + (int64_t)c0 * nb, mu, stream, a);
     });
   }
   return out;
@@ -457,11 +372,12 @@ std::vector<torch::Tensor> binned_multi_backward(torch::Tensor mu, torch::Tensor
                                                  Weights weights, std::vector<double> edges,
                                                  torch::Tensor g, bool need_mu, bool need_sigma,
                                                  std::vector<bool> need_w) {
-  MultiArgs a = make_multi_args(mu, sigma, weights, edges);
-  TORCH_CHECK(a.n > 0, "binned_multi_backward: empty input");
+  const MultiArgs base = make_multi_args(mu, sigma, weights, edges);
+  TORCH_CHECK(base.n > 0, "binned_multi_backward: empty input");
   const int C = (int)weights.size();
+  const int nb = base.nb;
   check_dev(g, "grad_out", at::kFloat);
-  TORCH_CHECK(g.numel() == (int64_t)C * a.nb, "grad_out must have C * nb elements");
+  TORCH_CHECK(g.numel() == (int64_t)C * nb, "grad_out must have C * nb elements");
   TORCH_CHECK((int)need_w.size() == C, "need_w: one flag per channel");
   bool any_w = false;
   for (int c = 0; c < C; ++c) {
@@ -470,39 +386,39 @@ std::vector<torch::Tensor> binned_multi_backward(torch::Tensor mu, torch::Tensor
     any_w = any_w || need_w[c];
   }
   TORCH_CHECK(need_mu || need_sigma || any_w, "no gradient requested");
-  const int nbp = multi_padded(a.nb);
+  const int nbp = padded_bins(nb, kOpMulti);
   std::vector<torch::Tensor> grads(2 + C);
-  if (need_mu) grads[0] = torch::empty({a.n}, mu.options());
-  if (need_sigma) grads[1] = torch::empty({sigma.numel()}, mu.options());
+  std::vector<float*> ptr(2 + C);
+  grads[0] = alloc_grad(need_mu, base.n, mu, ptr[0]);
+  grads[1] = alloc_grad(need_sigma, sigma.numel(), mu, ptr[1]);
   for (int c = 0; c < C; ++c)
-    if (need_w[c]) grads[2 + c] = torch::empty({weights[c]->numel()}, mu.options());
+    grads[2 + c] = alloc_grad(need_w[c], need_w[c] ? weights[c]->numel() : 0, mu, ptr[2 + c]);
   auto stream = at::hip::getCurrentHIPStream();
   for (int c0 = 0; c0 < C; c0 += kChanBlock) {
     const int nc = std::min(kChanBlock, C - c0);
-    set_channels(a, weights, c0, nc);
+    const MultiArgs a = with_channels(base, weights, c0, nc);
     MultiGrad o;
-    o.g = g.data_ptr<float>() + (int64_t)c0 * a.nb;
-    o.dmu = need_mu ? grads[0].data_ptr<float>() : nullptr;
-    o.dsigma = need_sigma ? grads[1].data_ptr<float>() : nullptr;
+    o.g = g.data_ptr<float>() + (int64_t)c0 * nb;
+    o.dmu = ptr[0];
+    o.dsigma = ptr[1];
     o.slab = nullptr;
     o.accum = c0 > 0;  // with mu or sigma wanted, every earlier pass ran and stored
+    // the [blocks, kRedCols] slab: sigma (added to an earlier pass's), four weights, unused
+    ReduceBwd r = {};
+    r.add0 = o.accum;
+    r.out[0] = a.sig_b ? o.dsigma : nullptr;
     bool pass_w = false;
     for (int c = 0; c < kChanBlock; ++c) {
-      o.dw[c] = c < nc && need_w[c0 + c] ? grads[2 + c0 + c].data_ptr<float>() : nullptr;
+      o.dw[c] = c < nc ? ptr[2 + c0 + c] : nullptr;
       pass_w = pass_w || o.dw[c] != nullptr;
+      r.out[1 + c] = (a.w_b >> c) & 1 ? o.dw[c] : nullptr;
     }
     if (!need_mu && !need_sigma && !pass_w) continue;
-    const bool red_sig = need_sigma && a.sig_b;
     MG_DISPATCH_MULTI(nbp, nc, {
-      with_bool(need_mu, [&](auto M) {
-        with_bool(need_sigma, [&](auto S) {
-          with_bool(pass_w, [&](auto W) {
-            constexpr bool kM = decltype(M)::value, kS = decltype(S)::value, kW = decltype(W)::value;
-            if constexpr (kM || kS || kW)
-              launch_multi_bwd<binned_multi_bwd_kernel<NB, CB, kM, kS, kW>>(a, o, mu, red_sig,
-                                                                            stream);
-          });
-        });
+      with_need3(need_mu, need_sigma, pass_w, [&](auto M, auto S, auto W) {
+        launch_slab_bwd<binned_multi_bwd_kernel<NB, CB, decltype(M)::value, decltype(S)::value,
+                                                decltype(W)::value>>(a, o, blocks_for(a.n),
+                                                                     kRedCols, r, mu, stream);
       });
     });
   }

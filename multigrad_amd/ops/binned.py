@@ -24,41 +24,16 @@ length N.  The first backward has no forward rule (no forward-over-reverse).
 """
 from __future__ import annotations
 
-import math
 from typing import Optional, Sequence, Tuple
 
-import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
+from ._binned_common import (_CHUNK, _INV_SQRT_2PI, MAX_BINS, _bcast, _check_operands,
+                             _host_edges, _native, _zero_grads)
 from ._ext import ext
 
 __all__ = ["gaussian_binned_sum", "MAX_BINS"]
-
-MAX_BINS = 32  # kMaxBins in csrc/smf_device.h
-_CHUNK = 1 << 16  # objects per chunk of the torch path
-_INV_SQRT_2PI = 1.0 / math.sqrt(2.0 * math.pi)
-
-
-def _host_edges(edges) -> Tuple[float, ...]:
-    if isinstance(edges, torch.Tensor):
-        if edges.device.type != "cpu":
-            raise TypeError(
-                "gaussian_binned_sum: `edges` must live on the host (a sequence, a numpy array "
-                "or a CPU tensor); convert a device tensor once at setup (tuple(edges.tolist())) "
-                "-- reading it back on every call would be a host sync inside a captured step")
-        edges = edges.detach().double().numpy()
-    e = np.asarray(edges, dtype=np.float64).reshape(-1)
-    nb = e.size - 1
-    if nb < 1 or nb > MAX_BINS:
-        raise ValueError(f"gaussian_binned_sum: need 1 <= nb <= {MAX_BINS} bins, got {nb}")
-    if not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
-        raise ValueError("gaussian_binned_sum: `edges` must be finite and strictly increasing")
-    return tuple(float(v) for v in e)
-
-
-def _bcast(t: torch.Tensor, lo: int, hi: int) -> torch.Tensor:
-    return t if t.numel() == 1 else t[lo:hi]
 
 
 def _torch_forward(mu, sigma, w, edges: Tuple[float, ...], chunk: int) -> torch.Tensor:
@@ -111,10 +86,6 @@ def _torch_backward(mu, sigma, w, edges: Tuple[float, ...], g, need, chunk: int)
             else:
                 dw[lo:hi] = d
     return dmu, dsig, dw
-
-
-def _native(mu: torch.Tensor) -> bool:
-    return mu.is_cuda and mu.dtype == torch.float32
 
 
 def _torch_jvp(mu, sigma, w, edges: Tuple[float, ...], tmu, tsigma, tw, chunk: int):
@@ -229,7 +200,7 @@ class _GaussianBinnedSumBackward(torch.autograd.Function):
         ctx.edges, ctx.chunk = edges, chunk
         ctx.save_for_backward(mu, sigma, w, g)
         if mu.numel() == 0:
-            grads = [torch.zeros_like(t) if k else None for t, k in zip((mu, sigma, w), need)]
+            grads = _zero_grads((mu, sigma, w), need)
         elif _native(mu):
             grads = ext().binned_backward(mu, sigma, w, list(edges), g, *need)
         else:
@@ -245,7 +216,7 @@ class _GaussianBinnedSumBackward(torch.autograd.Function):
         if not any(need) or (a is None and b is None and c is None):
             return (None,) * 7
         if mu.numel() == 0:
-            grads = [torch.zeros_like(t) if k else None for t, k in zip((mu, sigma, w, g), need)]
+            grads = _zero_grads((mu, sigma, w, g), need)
         elif _native(mu):
             a, b, c = (None if t is None else t.contiguous() for t in (a, b, c))
             grads = ext().binned_backward2(mu, sigma, w, list(ctx.edges), g, a, b, c, *need)
@@ -342,16 +313,7 @@ def gaussian_binned_sum(mu: torch.Tensor, sigma: torch.Tensor, edges: Sequence[f
     if not isinstance(mu, torch.Tensor) or not isinstance(sigma, torch.Tensor):
         raise TypeError("gaussian_binned_sum: mu and sigma must be tensors")
     e = _host_edges(edges)
-    n = mu.numel()
-    if sigma.numel() not in (n, 1):
-        raise ValueError(f"gaussian_binned_sum: sigma has {sigma.numel()} elements, "
-                         f"expected {n} or 1")
-    if weights is not None and weights.numel() not in (n, 1):
-        raise ValueError(f"gaussian_binned_sum: weights has {weights.numel()} elements, "
-                         f"expected {n} or 1")
-    for name, t in (("sigma", sigma), ("weights", weights)):
-        if t is not None and (t.dtype != mu.dtype or t.device != mu.device):
-            raise ValueError(f"gaussian_binned_sum: {name} must have mu's dtype and device")
+    _check_operands("gaussian_binned_sum", "mu", mu, (("sigma", sigma), ("weights", weights)))
     if not mu.dtype.is_floating_point:
         raise ValueError("gaussian_binned_sum: floating-point inputs required")
     flat = [None if t is None else t.reshape(-1).contiguous() for t in (mu, sigma, weights)]

@@ -44,8 +44,9 @@ from typing import Optional, Sequence, Tuple
 import torch
 from torch.autograd.function import once_differentiable
 
+from ._binned_common import (_CHUNK, _INV_SQRT_2PI, MAX_BINS, _bcast, _check_operands,
+                             _host_edges, _native, _zero_grads)
 from ._ext import ext
-from .binned import _CHUNK, _INV_SQRT_2PI, MAX_BINS, _bcast, _host_edges
 
 __all__ = ["gaussian_binned_sum_2d", "MAX_BINS"]
 
@@ -124,10 +125,6 @@ def _torch_backward(mux, sigx, muy, sigy, w, ex, ey, g, need, chunk: int):
     return grads
 
 
-def _native(mu: torch.Tensor) -> bool:
-    return mu.is_cuda and mu.dtype == torch.float32
-
-
 class _GaussianBinnedSum2d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mux, sigx, muy, sigy, w, ex, ey, chunk):
@@ -151,7 +148,7 @@ class _GaussianBinnedSum2d(torch.autograd.Function):
             return (None,) * 8
         mux = flat[0]
         if mux.numel() == 0:
-            grads = [torch.zeros_like(t) if k else None for t, k in zip(flat, need)]
+            grads = _zero_grads(flat, need)
         elif _native(mux):
             grads = ext().binned2d_backward(*flat, list(ctx.ex), list(ctx.ey),
                                             g.contiguous().float(), need)
@@ -197,13 +194,7 @@ def gaussian_binned_sum_2d(mu_x: torch.Tensor, sigma_x: torch.Tensor, mu_y: torc
     n = mu_x.numel()
     if mu_y.numel() != n:
         raise ValueError(f"gaussian_binned_sum_2d: mu_y has {mu_y.numel()} elements, expected {n}")
-    for name, t in (ops[1], ops[3], ("weights", weights)):
-        if t is not None and t.numel() not in (n, 1):
-            raise ValueError(f"gaussian_binned_sum_2d: {name} has {t.numel()} elements, "
-                             f"expected {n} or 1")
-    for name, t in ops[1:] + (("weights", weights),):
-        if t is not None and (t.dtype != mu_x.dtype or t.device != mu_x.device):
-            raise ValueError(f"gaussian_binned_sum_2d: {name} must have mu_x's dtype and device")
+    _check_operands("gaussian_binned_sum_2d", "mu_x", mu_x, ops[1:] + (("weights", weights),))
     if not mu_x.dtype.is_floating_point:
         raise ValueError("gaussian_binned_sum_2d: floating-point inputs required")
     return _GaussianBinnedSum2d.apply(mu_x, sigma_x, mu_y, sigma_y, weights, ex, ey,

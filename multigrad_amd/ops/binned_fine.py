@@ -72,9 +72,9 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
+from ._binned_common import _CHUNK, MAX_BINS, _check_operands, _native, _zero_grads
 from ._ext import ext
-from .binned import (_CHUNK, MAX_BINS, _native, _torch_backward, _torch_forward,
-                     gaussian_binned_sum)
+from .binned import _torch_backward, _torch_forward, gaussian_binned_sum
 
 __all__ = ["FineBins", "gaussian_binned_sum_fine", "MAX_FINE_BINS"]
 
@@ -148,7 +148,7 @@ class _GaussianBinnedSumFine(torch.autograd.Function):
         if not any(need):
             return (None,) * 5
         if mu.numel() == 0:
-            grads = [torch.zeros_like(t) if k else None for t, k in zip((mu, sigma, w), need)]
+            grads = _zero_grads((mu, sigma, w), need)
         elif _native(mu):
             grads = ext().binned_fine_backward(mu, sigma, w, ctx.bins.edges_dev,
                                                g.contiguous().float(), *need)
@@ -203,16 +203,10 @@ def gaussian_binned_sum_fine(bins: FineBins, mu: torch.Tensor, sigma: torch.Tens
         raise TypeError(f"{name}: mu and sigma must be tensors")
     if weights is not None and not isinstance(weights, torch.Tensor):
         raise TypeError(f"{name}: weights must be None or a tensor")
-    n = mu.numel()
     if not mu.dtype.is_floating_point:
         raise ValueError(f"{name}: mu must be a floating-point tensor")
-    for label, t in (("sigma", sigma), ("weights", weights)):
-        if t is None:
-            continue
-        if t.numel() not in (n, 1):
-            raise ValueError(f"{name}: {label} has {t.numel()} elements, expected {n} or 1")
-        if t.dtype != mu.dtype or t.device != mu.device:
-            raise ValueError(f"{name}: {label} must have mu's dtype and device")
+    for operand in (("sigma", sigma), ("weights", weights)):
+        _check_operands(name, "mu", mu, (operand,))
     if mu.device != bins.device:
         raise ValueError(f"{name}: mu lives on {mu.device}, the plan on {bins.device}; build "
                          f"the FineBins on the operands' device")

@@ -57,8 +57,9 @@ from typing import Optional, Sequence, Tuple
 import torch
 from torch.autograd.function import once_differentiable
 
+from ._binned_common import (_CHUNK, _INV_SQRT_2PI, MAX_BINS, _bcast, _check_operands,
+                             _host_edges, _zero_grads)
 from ._ext import ext
-from .binned import _CHUNK, _INV_SQRT_2PI, MAX_BINS, _bcast, _host_edges
 from .groups import GroupIndex
 
 __all__ = ["gaussian_binned_sum_by_group", "MAX_BINS"]
@@ -145,7 +146,7 @@ class _GaussianBinnedSumByGroup(torch.autograd.Function):
         if not any(need):
             return none
         if mu.numel() == 0:
-            grads = [torch.zeros_like(t) if k else None for t, k in zip((mu, sigma, w), need)]
+            grads = _zero_grads((mu, sigma, w), need)
         elif plan._native(mu):
             grads = ext().binned_group_backward(plan.ids, mu, sigma, w, list(ctx.edges),
                                                 g.contiguous().float(), *need)
@@ -209,13 +210,8 @@ def gaussian_binned_sum_by_group(plan: GroupIndex, mu: torch.Tensor, sigma: torc
         raise ValueError(f"{name}: mu has {mu.numel()} elements, expected {n} (the plan's N)")
     if not mu.dtype.is_floating_point:
         raise ValueError(f"{name}: mu must be a floating-point tensor")
-    for label, t in (("sigma", sigma), ("weights", weights)):
-        if t is None:
-            continue
-        if t.numel() not in (n, 1):
-            raise ValueError(f"{name}: {label} has {t.numel()} elements, expected {n} or 1")
-        if t.dtype != mu.dtype or t.device != mu.device:
-            raise ValueError(f"{name}: {label} must have mu's dtype and device")
+    for operand in (("sigma", sigma), ("weights", weights)):
+        _check_operands(name, "mu", mu, (operand,))
     if mu.device != plan.device:
         raise ValueError(f"{name}: operands live on {mu.device}, the plan on {plan.device}; "
                          f"build the GroupIndex from an index on the operands' device")

@@ -44,9 +44,10 @@ from typing import Optional, Sequence, Tuple
 import torch
 from torch.autograd.function import once_differentiable
 
+from ._binned_common import (_CHUNK, _INV_SQRT_2PI, MAX_BINS, _bcast, _check_operands,
+                             _host_edges, _native, _zero_grads)
 from ._ext import ext
-from .binned import (_CHUNK, _INV_SQRT_2PI, MAX_BINS, _bcast, _host_edges, _native,
-                     gaussian_binned_sum)
+from .binned import gaussian_binned_sum
 
 __all__ = ["gaussian_binned_sum_multi", "MAX_CHANNELS", "MAX_BINS"]
 
@@ -149,7 +150,7 @@ class _GaussianBinnedSumMulti(torch.autograd.Function):
             return none
         need = [need_mu, need_sigma] + need_w
         if mu.numel() == 0:
-            grads = [torch.zeros_like(t) if k else None for t, k in zip([mu, sigma] + ws, need)]
+            grads = _zero_grads([mu, sigma] + ws, need)
         elif _native(mu):
             grads = ext().binned_multi_backward(mu, sigma, ws, list(ctx.edges),
                                                 g.contiguous().float(), need_mu, need_sigma,
@@ -201,27 +202,19 @@ def gaussian_binned_sum_multi(mu: torch.Tensor, sigma: torch.Tensor, edges: Sequ
     if not isinstance(mu, torch.Tensor) or not isinstance(sigma, torch.Tensor):
         raise TypeError(f"{name}: mu and sigma must be tensors")
     e = _host_edges(edges)
-    n = mu.numel()
     if isinstance(weights, torch.Tensor) or not isinstance(weights, (list, tuple)):
         raise ValueError(f"{name}: `weights` must be a list or tuple with one entry per "
                          "channel (None or a tensor), not a single tensor")
     C = len(weights)
     if C < 1 or C > MAX_CHANNELS:
         raise ValueError(f"{name}: `weights` needs 1 <= C <= {MAX_CHANNELS} channels, got {C}")
-    if sigma.numel() not in (n, 1):
-        raise ValueError(f"{name}: sigma has {sigma.numel()} elements, expected {n} or 1")
-    if sigma.dtype != mu.dtype or sigma.device != mu.device:
-        raise ValueError(f"{name}: sigma must have mu's dtype and device")
+    _check_operands(name, "mu", mu, (("sigma", sigma),))
     for c, w in enumerate(weights):
         if w is None:
             continue
         if not isinstance(w, torch.Tensor):
             raise ValueError(f"{name}: weights[{c}] must be None or a tensor")
-        if w.numel() not in (n, 1):
-            raise ValueError(f"{name}: weights[{c}] has {w.numel()} elements, "
-                             f"expected {n} or 1")
-        if w.dtype != mu.dtype or w.device != mu.device:
-            raise ValueError(f"{name}: weights[{c}] must have mu's dtype and device")
+        _check_operands(name, "mu", mu, ((f"weights[{c}]", w),))
     if not mu.dtype.is_floating_point:
         raise ValueError(f"{name}: floating-point inputs required")
     if C == 1:

@@ -140,6 +140,19 @@ def test_broadcast_weights_and_everything_broadcast():
     _check(out, grads, ref, gref, absw)
 
 
+def test_everything_broadcast_over_several_workgroups():
+    """Three reduced gradients through the [blocks, 4] slab and its fixed-order reduce: 3001
+    objects, four per thread, are three workgroups of the backward."""
+    ex, ey = _edges(10, 6)
+    t = dict(_inputs(3001))
+    t["sigma_x"], t["sigma_y"] = t["sigma_x"][:1].clone(), t["sigma_y"][:1].clone()
+    t["w"] = torch.tensor([-0.7])
+    ref, gref, absw = _oracle(t, ex, ey, NAMES)
+    out, grads = _run(t, ex, ey, NAMES)
+    assert all(grads[k].shape == (1,) for k in ("sigma_x", "sigma_y", "w"))
+    _check(out, grads, ref, gref, absw)
+
+
 def test_edge_inputs_stay_finite_and_accurate():
     ex, ey = _edges(10, 6)
     t = {k: v.clone() for k, v in _inputs(1023).items()}
