@@ -23,7 +23,11 @@ __device__ __forceinline__ float dpdu(float at, float lo, float hi, int8_t k) {
     return 1.0f / (1.0f + r * r);
   }
   if (k == kLow || k == kHigh) {
-    const float q = at / sqrtf(at * at + 4.0f);
+    const float r = sqrtf(at * at + 4.0f);
+    // towards the bound 1 -+ at/r cancels (and is exactly 0 from |at| ~ 1e4): there
+    // dp/du = h/r with the distance to the bound h = 2/(r + |at|) = (r - |at|)/2
+    if (k == kLow ? at < 0.0f : at > 0.0f) return 2.0f / (r + fabsf(at)) / r;
+    const float q = at / r;
     return 0.5f * (k == kLow ? 1.0f + q : 1.0f - q);
   }
   return 1.0f;
@@ -33,11 +37,27 @@ __device__ __forceinline__ float inv_transform(float u, float lo, float hi, int8
   if (k == kBoth) {
     const float mid = (hi + lo) * 0.5f;
     const float s = (hi - lo) / kPi;
-    return mid + s * atanf(u / s);
+    // rounding can carry mid +- s*pi/2 past the box when u/s is large: clamp
+    return fminf(fmaxf(mid + s * atanf(u / s), lo), hi);
   }
-  if (k == kLow) return 0.5f * (2.0f * lo + u + sqrtf(u * u + 4.0f));
-  if (k == kHigh) return 0.5f * (2.0f * hi + u - sqrtf(u * u + 4.0f));
+  // one-sided: towards the bound u +- sqrt(u^2+4) cancels (p == bound exactly from
+  // |u| ~ 1e4), so the distance to the bound is formed as h = 2/(sqrt(u^2+4) + |u|)
+  if (k == kLow) {
+    const float r = sqrtf(u * u + 4.0f);
+    return u < 0.0f ? lo + 2.0f / (r - u) : 0.5f * (2.0f * lo + u + r);
+  }
+  if (k == kHigh) {
+    const float r = sqrtf(u * u + 4.0f);
+    return u > 0.0f ? hi - 2.0f / (r + u) : 0.5f * (2.0f * hi + u - r);
+  }
   return u;
+}
+
+// Bias correction 1 - b^t of the 1-based step t.  Not 1.0f - powf(b, t): the rounding of
+// b^t is left over in full after the subtraction, which for b2 = 0.999 is 110 * 2^-24 of
+// 1 - b2^2 at the second step (and half that in the step taken), against 2-3 * 2^-24 here.
+__device__ __forceinline__ float bias_correction(float b, int t) {
+  return -expm1f((float)t * logf(b));
 }
 
 // One Adam step of one coordinate.  H: any struct with lr, b1, b2, eps.  bc1/bc2 are the

@@ -55,8 +55,8 @@ __global__ __launch_bounds__(kAdamThreads) void fused_adam_kernel(AdamArgs a) {
   const int step = a.host_step >= 0
                        ? a.host_step
                        : __hip_atomic_load(a.step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const float bc1 = 1.0f - powf(a.b1, (float)(step + 1));
-  const float bc2 = 1.0f - powf(a.b2, (float)(step + 1));
+  const float bc1 = bias_correction(a.b1, step + 1);
+  const float bc2 = bias_correction(a.b2, step + 1);
   float* trow = a.traj ? a.traj + (int64_t)(step + 1) * a.traj_stride : nullptr;
   const int64_t tid = (int64_t)blockIdx.x * kAdamThreads + threadIdx.x;
   const int64_t nthr = (int64_t)gridDim.x * kAdamThreads;

@@ -320,8 +320,8 @@ __device__ __forceinline__ void smf2_finish(const Smf2Step& P, const SmfBins& b,
         nt.x = th.x - P.lr * gr.x;
         nt.y = th.y - P.lr * gr.y;
       } else {           // reference multigrad/adam.py:52-68 (csrc/adam.h, same bits)
-        const float bc1 = 1.0f - powf(P.b1, (float)(s + 1));
-        const float bc2 = 1.0f - powf(P.b2, (float)(s + 1));
+        const float bc1 = bias_correction(P.b1, s + 1);
+        const float bc2 = bias_correction(P.b2, s + 1);
         struct { float lr, b1, b2, eps; } hp{P.lr, P.b1, P.b2, P.aeps};
         const float gg[2] = {gr.x, gr.y};
         const float po[2] = {th.x, th.y};

@@ -57,7 +57,12 @@ __device__ __forceinline__ float dpdu_fast(float at, float lo, float hi, int8_t 
     return __builtin_amdgcn_rcpf(fmaf(r, r, 1.0f));
   }
   if (k == kLow || k == kHigh) {
-    const float q = at * __builtin_amdgcn_rsqf(fmaf(at, at, 4.0f));
+    const float x = fmaf(at, at, 4.0f);
+    const float rs = __builtin_amdgcn_rsqf(x);
+    // towards the bound: h/r with h = 2/(r + |at|), r = x * rs (no cancellation, as adam.h)
+    if (k == kLow ? at < 0.0f : at > 0.0f)
+      return 2.0f * __builtin_amdgcn_rcpf(fmaf(x, rs, fabsf(at))) * rs;
+    const float q = at * rs;
     return 0.5f * (k == kLow ? 1.0f + q : 1.0f - q);
   }
   return 1.0f;
@@ -66,10 +71,18 @@ __device__ __forceinline__ float dpdu_fast(float at, float lo, float hi, int8_t 
 __device__ __forceinline__ float inv_transform_fast(float u, float lo, float hi, int8_t k) {
   if (k == kBoth) {
     const float s = (hi - lo) * (1.0f / kPi);
-    return fmaf(s, atanf(u * __builtin_amdgcn_rcpf(s)), (hi + lo) * 0.5f);
+    const float p = fmaf(s, atanf(u * __builtin_amdgcn_rcpf(s)), (hi + lo) * 0.5f);
+    return fminf(fmaxf(p, lo), hi);  // stays in the box, as adam.h
   }
-  if (k == kLow) return 0.5f * (2.0f * lo + u + __builtin_amdgcn_sqrtf(fmaf(u, u, 4.0f)));
-  if (k == kHigh) return 0.5f * (2.0f * hi + u - __builtin_amdgcn_sqrtf(fmaf(u, u, 4.0f)));
+  // one-sided: the distance to the bound is 2/(sqrt(u^2+4) + |u|) on the side towards it
+  if (k == kLow) {
+    const float r = __builtin_amdgcn_sqrtf(fmaf(u, u, 4.0f));
+    return u < 0.0f ? fmaf(2.0f, __builtin_amdgcn_rcpf(r - u), lo) : 0.5f * (2.0f * lo + u + r);
+  }
+  if (k == kHigh) {
+    const float r = __builtin_amdgcn_sqrtf(fmaf(u, u, 4.0f));
+    return u > 0.0f ? fmaf(-2.0f, __builtin_amdgcn_rcpf(r + u), hi) : 0.5f * (2.0f * hi + u - r);
+  }
   return u;
 }
 
@@ -422,8 +435,8 @@ __global__ __launch_bounds__(kThreads, MG_LANES_MINWAVES) void smf_fwd_lanes_ker
     // reciprocal bias corrections (uniform): the per-population update below is multiply /
     // v_rcp / v_sqrt instead of three IEEE divisions per parameter (~30 VALU ops each),
     // within an ulp or two of the division form (csrc/adam.hip, the stand-alone kernels)
-    ubc1 = 1.0f / (1.0f - powf(upd.b1, (float)(st + 1)));
-    ubc2 = 1.0f / (1.0f - powf(upd.b2, (float)(st + 1)));
+    ubc1 = 1.0f / bias_correction(upd.b1, st + 1);
+    ubc2 = 1.0f / bias_correction(upd.b2, st + 1);
     if (upd.traj) utrow = upd.traj + (int64_t)(st + 1) * upd.traj_stride;
   }
   // UPD: the update inputs of a group (its residual block, 1 KB per dwordx4 instruction, and
@@ -739,8 +752,8 @@ __global__ __launch_bounds__(kThreads) void smf_vjp_lanes_kernel(
     const int st = adam.host_step >= 0
                        ? adam.host_step
                        : __hip_atomic_load(adam.step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    bc1 = 1.0f - powf(adam.b1, (float)(st + 1));
-    bc2 = 1.0f - powf(adam.b2, (float)(st + 1));
+    bc1 = bias_correction(adam.b1, st + 1);
+    bc2 = bias_correction(adam.b2, st + 1);
     if (adam.traj)
       trow = reinterpret_cast<float2*>(reinterpret_cast<float*>(adam.traj) +
                                        (int64_t)(st + 1) * adam.traj_stride);

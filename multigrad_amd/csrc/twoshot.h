@@ -71,8 +71,8 @@ __device__ __forceinline__ void twoshot_block(const TwoShotArgs& a, int bid, int
   // before that launch ended, and this launch is ordered after it
   if (bid == 0 && (int)threadIdx.x < a.size) uc_signal(ts_gflag(a.f.base[threadIdx.x]) + a.rank, seq);
   const int bad = ts_wait_all(ts_gflag(me), a.size, seq, a.err, a.ticks, lds + 1);
-  const float bc1 = 1.0f - powf(a.b1, (float)(st + 1));
-  const float bc2 = 1.0f - powf(a.b2, (float)(st + 1));
+  const float bc1 = bias_correction(a.b1, st + 1);
+  const float bc2 = bias_correction(a.b2, st + 1);
   float* trow = a.traj ? a.traj + (int64_t)(st + 1) * a.traj_stride : nullptr;
   const float* own = reinterpret_cast<const float*>(a.t.base[a.rank]) + a.lo;
   const int64_t n4 = a.n >> 2;

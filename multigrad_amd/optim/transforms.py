@@ -6,12 +6,19 @@ Each bounded parameter ``p`` is optimised in an unbounded coordinate ``u = T(p)`
 bounds             u = T(p)                     p = T^-1(u)                     dp/du
 =================  ===========================  ==============================  =====================
 both finite        s tan((p - mid)/s)           mid + s atan(u/s)               1/(1 + (u/s)^2)
-low only           p - lo + 1/(lo - p)          (2 lo + u + sqrt(u^2+4))/2      (1 + u/sqrt(u^2+4))/2
-high only          p - hi + 1/(hi - p)          (2 hi + u - sqrt(u^2+4))/2      (1 - u/sqrt(u^2+4))/2
+low only           p - lo + 1/(lo - p)          lo + h(u)                       h(u)/sqrt(u^2+4)
+high only          p - hi + 1/(hi - p)          hi - h(-u)                      h(-u)/sqrt(u^2+4)
 none               p                            u                               1
 =================  ===========================  ==============================  =====================
 
-with ``mid = (lo+hi)/2`` and ``s = (hi-lo)/pi``.  The reference builds a dense
+with ``mid = (lo+hi)/2``, ``s = (hi-lo)/pi`` and the distance to a one-sided bound
+``h(u) = (u + sqrt(u^2+4))/2``.  Towards the bound (``u < 0``) that difference cancels in
+floating point -- in float32 it is exactly 0 from ``|u| ~ 1e4``, which would put the
+parameter on its bound with ``dp/du = 0`` for good -- so there ``h`` is evaluated as
+``2/(sqrt(u^2+4) + |u|)``; away from the bound the expressions are
+``(2 lo + u + sqrt(u^2+4))/2`` and ``(1 + u/sqrt(u^2+4))/2`` (mirrored for a high bound).
+The two-sided result is clamped into ``[lo, hi]``: for ``|u/s|`` large, rounding would
+otherwise carry ``mid +- s pi/2`` past the box.  The reference builds a dense
 ``P x P`` ``jax.jacobian`` of the inverse transform and evaluates it at the *bounded*
 parameters; the Jacobian is diagonal, so here it is the elementwise
 ``dp/du`` evaluated at ``u`` (``legacy=True`` evaluates it at ``p`` for bit-parity).
@@ -113,17 +120,20 @@ class Bounds:
     def inverse(self, u: torch.Tensor) -> torch.Tensor:
         k, lo, hi, mid, s = self._safe(u)
         r = torch.sqrt(u * u + 4)
-        both = torch.where(k == KIND_BOTH, mid + s * torch.atan(u / s), u)
-        low = torch.where(k == KIND_LOW, 0.5 * (2 * lo + u + r), both)
-        return torch.where(k == KIND_HIGH, 0.5 * (2 * hi + u - r), low)
+        h = 2.0 / (r + u.abs())  # distance to a one-sided bound on the side towards it
+        box = torch.minimum(torch.maximum(mid + s * torch.atan(u / s), lo), hi)
+        both = torch.where(k == KIND_BOTH, box, u)
+        low = torch.where(k == KIND_LOW, torch.where(u < 0, lo + h, 0.5 * (2 * lo + u + r)), both)
+        return torch.where(k == KIND_HIGH, torch.where(u > 0, hi - h, 0.5 * (2 * hi + u - r)), low)
 
     def dpdu(self, u: torch.Tensor) -> torch.Tensor:
         k, lo, hi, mid, s = self._safe(u)
         r = torch.sqrt(u * u + 4)
         one = torch.ones_like(u)
+        hr = 2.0 / (r + u.abs()) / r  # h/r: dp/du on the side towards a one-sided bound
         both = torch.where(k == KIND_BOTH, 1.0 / (1.0 + (u / s) ** 2), one)
-        low = torch.where(k == KIND_LOW, 0.5 * (1 + u / r), both)
-        return torch.where(k == KIND_HIGH, 0.5 * (1 - u / r), low)
+        low = torch.where(k == KIND_LOW, torch.where(u < 0, hr, 0.5 * (1 + u / r)), both)
+        return torch.where(k == KIND_HIGH, torch.where(u > 0, hr, 0.5 * (1 - u / r)), low)
 
 
 def transform(param, bounds):
@@ -146,11 +156,13 @@ def inverse_transform(uparam, bounds):
     u = torch.as_tensor(uparam, dtype=torch.float32) if not isinstance(uparam, torch.Tensor) else uparam
     if lo is not None and hi is not None:
         mid, s = (hi + lo) / 2.0, (hi - lo) / math.pi
-        return mid + s * torch.atan(u / s)
+        return torch.clamp(mid + s * torch.atan(u / s), lo, hi)
+    # one-sided: towards the bound the distance to it is 2/(sqrt(u^2+4) + |u|) (no cancellation)
+    r = torch.sqrt(u ** 2 + 4)
     if lo is not None:
-        return 0.5 * (2.0 * lo + u + torch.sqrt(u ** 2 + 4))
+        return torch.where(u < 0, lo + 2.0 / (r - u), 0.5 * (2.0 * lo + u + r))
     if hi is not None:
-        return 0.5 * (2.0 * hi + u - torch.sqrt(u ** 2 + 4))
+        return torch.where(u > 0, hi - 2.0 / (r + u), 0.5 * (2.0 * hi + u - r))
     return u
 
 

@@ -447,6 +447,57 @@ def test_bounded_pipelined_update_matches_unpipelined(monkeypatch, owner, graph,
     assert float((t[-1] - t[0]).abs().max()) > 1e-3  # the fit moved
 
 
+@pytest.mark.parametrize("graph,kind", [(False, "both"), (True, "mixed")])
+def test_bounded_update_next_to_a_lower_bound(monkeypatch, graph, kind):
+    """Every fourth population's `a` starts 1e-4 above a lower bound (u ~ -1e4, where the
+    cancelling one-sided forms gave p == lo and dp/du == 0 exactly: such a coordinate was
+    recorded on its bound and could never move).  Both schedules -- the stand-alone bounded
+    Adam kernel and the update folded into the lanes forward, the only user of its
+    hardware-reciprocal copies of the transforms -- keep those coordinates strictly above
+    the bound and move them.  A step of lr in u changes p - lo by 1e-8 lr, far below the
+    float32 spacing of p, so the distance to the bound is read from the engine's u:
+    h(u) = 2/(sqrt(u^2+4) + |u|) changes exactly when u does.  The gradient on `a` is about
+    1e-4 here, so |g dp/du| ~ 1e-12: under Adam's default eps = 1e-8 a step would be
+    lr * 1e-4 = 2e-6, below the float32 spacing 1e-3 of u at 1e4, whatever the transforms do;
+    the run takes eps = 1e-12, which leaves steps of about lr/2."""
+    from multigrad_amd.engine.fused import FusedAdamEngine
+    from multigrad_amd.models.population import PopulationSMFModel, make_population_data
+    from multigrad_amd.optim.transforms import Bounds
+    data = make_population_data(num_params=6000, num_halos=300_000, seed=12, device=DEV)
+    model = PopulationSMFModel(aux_data=data)
+    model.set_target_from_truth()
+    g = data["guess"].detach().cpu()
+    bounds = torch.stack([g - 0.3, g + 0.2], 1).numpy()
+    if kind == "mixed":
+        bounds[0::2, 1] = np.inf      # a: lower bound only
+        bounds[1::4, 0] = -np.inf     # some log sigmas: upper bound only
+    tight = torch.zeros(g.numel(), dtype=torch.bool)
+    tight[0::8] = True                # a of every fourth population
+    bounds[0::8, 0] = (g[0::8] - 1e-4).numpy()
+    bounds[0::8, 1] = np.inf
+    tight = tight.to(DEV)
+    kw = dict(learning_rate=2e-2, param_bounds=bounds, eps=1e-12)
+    b = Bounds.from_spec(bounds, g.numel(), device=DEV)
+    out = {}
+    for pipe in ("0", "1"):
+        monkeypatch.setenv("MULTIGRAD_PIPELINE", pipe)
+        eng = FusedAdamEngine(model, graph=graph)
+        t = eng.run_adam(data["guess"], nsteps=8, **kw)
+        assert eng.pipeline == (pipe == "1") and eng.bounds is not None
+        out[pipe] = t
+        assert bool(torch.isfinite(t).all())
+        assert bool(((t >= b.lo) & (t <= b.hi)).all())
+        assert bool((t[:, tight] > b.lo[tight]).all()), "a tight coordinate sits on its bound"
+        u0 = b.forward(t[0])          # the engine's start: u = T(recorded guess)
+        u8 = eng.to_user(eng.u[:eng.P].clone())
+        assert bool(torch.isfinite(u0[tight]).all())
+        assert bool((u8[tight] != u0[tight]).all()), "a tight coordinate did not move"
+        m8 = eng.to_user(eng.m[:eng.P].clone())
+        assert bool((m8[tight] != 0).all()), "dp/du == 0 on a tight coordinate"
+    torch.testing.assert_close(out["1"], out["0"], rtol=2e-6, atol=2e-7)
+    assert float((out["1"][-1] - out["1"][0]).abs().max()) > 1e-3  # the fit moved
+
+
 @pytest.mark.parametrize("owner,graph,history", [(False, True, "full"), (False, False, "full"),
                                                  (False, True, "last"), (True, False, "full"),
                                                  (True, True, 2)])

@@ -224,3 +224,83 @@ def test_bounds_from_numeric_array_equals_list_spec():
     assert torch.equal(b_arr.kind, b_lst.kind)
     b_t = Bounds.from_spec(torch.as_tensor(arr), n, dtype=torch.float64)
     assert torch.equal(b_t.kind, b_lst.kind)
+
+
+# ---------------------------------------------------------------------------------------
+# Bound transforms near the bounds, float32 against the float64 oracle of bounds_oracle.py.
+# Contract (e = 2^-24, h = |p - bound|):  |p - p64| <= e max(|bound|, |p64|) + C e h64  and
+# |dp/du - d64| <= C e d64 for one-sided bounds at u in +-[1e-3, 1e6];  lo <= p <= hi and
+# |p - p64| <= C e max(|lo|, |hi|) for two-sided ones at |u| up to 1e15.  C = 16: the largest
+# measured error/bound ratios are 5.95 (distance: bound +-9, side away from the bound, where
+# the kept expression (2 lo + u + r)/2 rounds twice at magnitude 2 lo; first-order worst case
+# (18 + 20)/2 - 10 + 1.5 = 10.5), 4.22 (dp/du) and 3.84 (two-sided); 4x the ratio, capped at 16.
+C_BOUND = 16
+_ONE_SIDED = [((0.0, None), 2), ((9.0, None), 2), ((None, 0.0), 3), ((None, -9.0), 3)]
+
+
+@pytest.mark.parametrize("spec,kind", _ONE_SIDED)
+def test_one_sided_transform_float32_near_bound(spec, kind):
+    import bounds_oracle as O
+    u = O.log_u()
+    n = u.numel()
+    b = Bounds.from_spec([spec] * n, n)
+    assert b.lo.dtype == torch.float32
+    low = kind == O.LOW
+    bd = (b.lo if low else b.hi).double()
+    h64, d64 = O.dist64(u, kind)
+    p64 = bd + h64 if low else bd - h64
+    tol = O.E * torch.maximum(bd.abs(), p64.abs()) + C_BOUND * O.E * h64
+    for p in (b.inverse(u), A.inverse_transform(u, spec)):
+        assert p.dtype == torch.float32 and torch.isfinite(p).all()
+        assert bool(((p.double() - p64).abs() <= tol).all())
+        # strictly inside wherever the exact result is more than 2 float32 ulps off the bound
+        far = h64 > 2 * O.ulp32(bd)
+        assert bool((p.double() > bd)[far].all() if low else (p.double() < bd)[far].all())
+    d = b.dpdu(u)
+    assert d.dtype == torch.float32 and bool((d > 0).all())
+    assert bool(((d.double() - d64).abs() <= C_BOUND * O.E * d64).all())
+    # round trip T(T^-1(u)) at |u| <= 1e4: du/dp = 1 + 1/h^2 carries the error allowed in p
+    # (and, for a non-zero bound, the rounding of p itself) back into u
+    m = u.abs() <= 1e4
+    back = b.forward(b.inverse(u)).double()
+    rt = (1 + 1 / h64 ** 2) * tol + 4 * O.E * u.double().abs()
+    assert bool(torch.isfinite(back[m]).all())
+    assert bool(((back - u.double()).abs() <= rt)[m].all())
+
+
+def test_two_sided_transform_float32_stays_in_box():
+    import bounds_oracle as O
+    lo, hi = O.random_boxes()
+    b = Bounds(lo, hi, torch.full((lo.numel(),), O.BOTH, dtype=torch.int8))
+    scale = torch.maximum(lo.abs(), hi.abs()).double()
+    for a in (1.0, 1e3, 1e6, 1e9, 1e15):
+        for s in (1.0, -1.0):
+            u = torch.full_like(lo, s * a)
+            p, d = b.inverse(u), b.dpdu(u)
+            p64, _ = O.inverse64(u, lo, hi, b.kind)
+            assert bool(((p >= lo) & (p <= hi)).all()), (a, s)
+            assert bool(((p.double() - p64).abs() <= C_BOUND * O.E * scale).all()), (a, s)
+            assert bool((torch.isfinite(d) & (d >= 0)).all()), (a, s)
+    # the scalar helper clamps too: the narrowest box, far out
+    i = int((hi - lo).argmin())
+    box = (float(lo[i]), float(hi[i]))
+    for uu in (1e9, -1e9):
+        p = float(A.inverse_transform(torch.tensor(uu), box))
+        assert box[0] <= p <= box[1]
+
+
+@pytest.mark.parametrize("lo,lr", [(0.0, 0.01), (1.0, 100.0)])
+def test_adam_guess_next_to_lower_bound_is_not_frozen(lo, lr):
+    """A guess 1e-4 above its lower bound (u ~ -1e4) is recorded strictly above the bound
+    and one update with a negative gradient moves it.  (With lo = 1 a step of lr = 0.01 in
+    u changes p by 1e-10, below float32 resolution at 1: that case takes lr = 100.)"""
+    p0 = torch.tensor([lo + 1e-4, lo + 0.5], dtype=torch.float32)
+    b = Bounds.from_spec([(lo, None), (lo, None)], 2)
+    opt = A.Adam(p0, lr, bounds=b)
+    start = opt.params().clone()
+    assert bool((start > lo).all())
+    torch.testing.assert_close(start, p0, rtol=1e-2, atol=0)  # 1e-4 resolved at lo = 1
+    u0 = opt.u.clone()
+    opt.update(torch.tensor([-1.0, -1.0]))
+    assert bool((opt.u > u0).all())
+    assert bool((opt.params() > start).all())
