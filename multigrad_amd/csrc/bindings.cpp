@@ -124,6 +124,16 @@ void lincomb_cols(torch::Tensor H, int64_t nrows, torch::Tensor coef, double alp
                   c10::optional<torch::Tensor> post, int64_t n, torch::Tensor y);
 void compact_diag(torch::Tensor H, torch::Tensor rows, torch::Tensor fac, torch::Tensor Q,
                   double h0, c10::optional<torch::Tensor> scale, int64_t n, torch::Tensor out);
+// hmc.hip
+int64_t hmc_workspace();
+void hmc_leapfrog(torch::Tensor q, torch::Tensor p, torch::Tensor g, torch::Tensor inv_mass,
+                  double a, double b, c10::optional<torch::Tensor> ke_out,
+                  c10::optional<torch::Tensor> ws);
+void hmc_momentum(torch::Tensor z, torch::Tensor inv_mass, torch::Tensor p,
+                  c10::optional<torch::Tensor> ke_out, c10::optional<torch::Tensor> ws);
+void hmc_commit(torch::Tensor q, int64_t count, c10::optional<torch::Tensor> mean,
+                c10::optional<torch::Tensor> m2, c10::optional<torch::Tensor> track_idx,
+                c10::optional<torch::Tensor> track_row, c10::optional<torch::Tensor> sample_row);
 // binned.hip
 torch::Tensor binned_forward(torch::Tensor mu, torch::Tensor sigma, c10::optional<torch::Tensor> w,
                              std::vector<double> edges);
@@ -275,6 +285,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("lincomb", &mg::lincomb);
   m.def("lincomb_cols", &mg::lincomb_cols);
   m.def("compact_diag", &mg::compact_diag);
+  m.def("hmc_workspace", &mg::hmc_workspace);
+  m.def("hmc_leapfrog", &mg::hmc_leapfrog);
+  m.def("hmc_momentum", &mg::hmc_momentum);
+  m.def("hmc_commit", &mg::hmc_commit);
   m.def("binned_forward", &mg::binned_forward);
   m.def("binned_backward", &mg::binned_backward);
   m.def("binned_backward2", &mg::binned_backward2);

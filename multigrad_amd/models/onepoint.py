@@ -228,6 +228,45 @@ class _OptimizerFrontEnds:
                                        param_bounds=param_bounds, randkey=randkey, comm=comm,
                                        history=hist, **kw)
 
+    def run_hmc(self, guess, nsamples: int = 1000, warmup: int = 500, nleapfrog: int = 10,
+                step_size: float = 0.1, param_bounds=None, randkey=0, loss_scale: float = 1.0,
+                history: str = "full", track=None, comm=None, **kw):
+        """Draw from the posterior ``exp(-loss_scale * loss)`` by Hamiltonian Monte Carlo
+        (:mod:`multigrad_amd.optim.hmc`); returns an
+        :class:`~multigrad_amd.optim.hmc.HMCResult` on every rank.
+
+        ``loss_scale = 0.5`` makes a chi^2 loss a Gaussian log-likelihood.  ``warmup``
+        iterations adapt the step size (dual averaging) and the diagonal mass (Stan's windows)
+        from ``step_size``; ``randkey`` (int or key) seeds the sampler.  ``history="full"``
+        returns ``samples [nsamples, P]``; ``history="moments"`` only ``mean`` and ``var``
+        (with ``track=indices`` for the chains of a few parameters: the intended use at 1e7
+        parameters).  With ``param_bounds`` the chain runs in the unbounded coordinates of
+        :mod:`~multigrad_amd.optim.transforms` with a flat prior on the bounded parameters.
+        Models with the fused-engine protocol (and no bounds) sample over the engine's
+        (ZeRO- or owner-) sharded vectors, the evaluations of a trajectory staying on the
+        device; everything else goes through ``calc_loss_and_grad_from_params``.  Extra
+        keywords (``jitter``, ``noise``, ``target_accept``, ``adapt_step_size``,
+        ``adapt_mass``, ``inv_mass``) go to :func:`multigrad_amd.optim.hmc.hmc_sample`."""
+        from ..optim import hmc as _hmc
+        from ..optim.lbfgs import GenericObjective
+        from ..optim.transforms import Bounds
+        comm = self._opt_comm() if comm is None else comm
+        x0 = as_param_tensor(guess, device=self.param_device())
+        skw = dict(nsamples=nsamples, warmup=warmup, nleapfrog=nleapfrog, step_size=step_size,
+                   loss_scale=loss_scale, seed=randkey, history=history, track=track)
+        fused = getattr(self, "fused_engine", None)
+        if fused is not None and param_bounds is None:
+            eng = fused(comm=comm, **{k: kw.pop(k) for k in ("zero", "chunks") if k in kw})
+            if eng is not None:
+                try:
+                    return _hmc.hmc_sample(eng.lbfgs_objective(x0), **skw, **kw)
+                finally:
+                    if not getattr(eng, "cached", False):
+                        eng.close()
+        bounds = Bounds.from_spec(param_bounds, x0.numel(), device=x0.device, dtype=torch.float32)
+        obj = GenericObjective(self.calc_loss_and_grad_from_params, x0, comm=comm, bounds=bounds)
+        return _hmc.hmc_sample(obj, **skw, **kw)
+
 
 @dataclass
 class OnePointModel(_OptimizerFrontEnds):

@@ -135,6 +135,34 @@ class Bounds:
         low = torch.where(k == KIND_LOW, torch.where(u < 0, hr, 0.5 * (1 + u / r)), both)
         return torch.where(k == KIND_HIGH, torch.where(u > 0, hr, 0.5 * (1 - u / r)), low)
 
+    def log_dpdu(self, u: torch.Tensor) -> torch.Tensor:
+        """``log dp/du``, the log-Jacobian a sampler in ``u`` adds for a flat prior on ``p``.
+        Two-sided: ``-log1p((u/s)^2)``.  One-sided, with ``v = u`` for a low and ``v = -u``
+        for a high bound: towards the bound (``v < 0``) ``log(h/r)`` with the cancellation-free
+        ``h`` of :meth:`dpdu`; away from it ``dp/du = 1 - 2/((r + v) r)`` (the same value as
+        ``(1 + v/r)/2``, written so that the logarithm keeps its digits as ``dp/du -> 1``)."""
+        k, lo, hi, mid, s = self._safe(u)
+        r = torch.sqrt(u * u + 4)
+        a = u.abs()
+        toward = math.log(2.0) - torch.log(r + a) - torch.log(r)
+        away = torch.log1p(-2.0 / ((r + a) * r))
+        both = torch.where(k == KIND_BOTH, -torch.log1p((u / s) ** 2), torch.zeros_like(u))
+        low = torch.where(k == KIND_LOW, torch.where(u < 0, toward, away), both)
+        return torch.where(k == KIND_HIGH, torch.where(u > 0, toward, away), low)
+
+    def dlog_dpdu(self, u: torch.Tensor) -> torch.Tensor:
+        """``d/du log dp/du``.  Two-sided: ``-2u/(s^2 + u^2)``.  One-sided (``v`` as in
+        :meth:`log_dpdu`): ``d/dv log(h/r) = (r - v)/r^2``, evaluated as ``(r + |v|)/r^2``
+        towards the bound and ``4/((r + v) r^2)`` away from it; a high bound flips the sign."""
+        k, lo, hi, mid, s = self._safe(u)
+        r = torch.sqrt(u * u + 4)
+        a = u.abs()
+        toward = (r + a) / (r * r)
+        away = 4.0 / ((r + a) * r * r)
+        both = torch.where(k == KIND_BOTH, -2.0 * u / (s * s + u * u), torch.zeros_like(u))
+        low = torch.where(k == KIND_LOW, torch.where(u < 0, toward, away), both)
+        return torch.where(k == KIND_HIGH, -torch.where(u > 0, toward, away), low)
+
 
 def transform(param, bounds):
     """Transform one bounded parameter into its unbounded coordinate."""
