@@ -215,7 +215,7 @@ void multi_dot(torch::Tensor A, int64_t nrows, std::vector<torch::Tensor> B, int
   TORCH_CHECK(out.scalar_type() == at::kDouble && workspace.scalar_type() == at::kDouble, "fp64 out");
   TORCH_CHECK(A.dim() == 2 && A.stride(1) == 1, "A must be row-major 2-d");
   TORCH_CHECK(nrows >= 1 && nrows <= A.size(0) && nc >= 1 && nc <= kMaxCols, "bad shape");
-  TORCH_CHECK(n <= A.size(1), "n too large");
+  TORCH_CHECK(n >= 0 && n <= A.size(1), "n must be in 0..A.size(1)");
   TORCH_CHECK(out.numel() >= nrows * nc, "out too small");
   RowPtrs rp;
   for (int c = 0; c < kMaxCols; ++c) rp.p[c] = nullptr;
@@ -262,11 +262,14 @@ void lincomb(torch::Tensor H, int64_t nrows, torch::Tensor coef, double alpha,
   TORCH_CHECK(H.is_cuda() && coef.is_cuda() && y.is_cuda(), "device tensors");
   TORCH_CHECK(H.scalar_type() == at::kFloat && coef.scalar_type() == at::kFloat &&
               y.scalar_type() == at::kFloat, "fp32");
+  TORCH_CHECK(n >= 0 && nrows >= 0, "bad sizes");
   TORCH_CHECK(H.dim() == 2 && H.stride(1) == 1 && nrows <= H.size(0) && nrows <= kLincombRows &&
               coef.numel() >= nrows && n <= H.size(1) && y.numel() >= n, "bad shapes");
+  TORCH_CHECK(coef.is_contiguous() && y.is_contiguous(), "coef, y must be contiguous");
   const float* xp = nullptr;
   if (x.has_value() && x->defined()) {
-    TORCH_CHECK(x->is_cuda() && x->scalar_type() == at::kFloat && x->numel() >= n, "bad x");
+    TORCH_CHECK(x->is_cuda() && x->scalar_type() == at::kFloat && x->is_contiguous() &&
+                x->numel() >= n, "x: contiguous fp32 device vector, >= n");
     xp = x->data_ptr<float>();
   }
   auto stream = at::hip::getCurrentHIPStream();

@@ -37,6 +37,8 @@ def lincomb_(H: torch.Tensor, nrows: int, coef: torch.Tensor, alpha: float,
              x: Optional[torch.Tensor], y: torch.Tensor) -> torch.Tensor:
     """``y = alpha * x + sum_i coef[i] * H[i]`` (one fused pass on the GPU)."""
     n = y.numel()
+    if not 0 <= nrows <= 256:
+        raise ValueError(f"lincomb_ takes 0..256 rows, got {nrows}")
     if y.device.type == "cuda":
         ext().lincomb(H, int(nrows), coef, float(alpha), x, n, y)
         return y
