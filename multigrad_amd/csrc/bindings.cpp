@@ -124,6 +124,13 @@ void lincomb_cols(torch::Tensor H, int64_t nrows, torch::Tensor coef, double alp
                   c10::optional<torch::Tensor> post, int64_t n, torch::Tensor y);
 void compact_diag(torch::Tensor H, torch::Tensor rows, torch::Tensor fac, torch::Tensor Q,
                   double h0, c10::optional<torch::Tensor> scale, int64_t n, torch::Tensor out);
+// gram.hip
+torch::Tensor weighted_gram(torch::Tensor J, c10::optional<torch::Tensor> w, int64_t nrows);
+// smf_jacobian.hip
+void smf_jacobian_lanes(torch::Tensor slot_pop, torch::Tensor slot_part, torch::Tensor theta,
+                        torch::Tensor resid, int64_t s0, int64_t s1, std::vector<double> scale,
+                        bool log_sigma, torch::Tensor jac, torch::Tensor partials, int64_t nparts,
+                        torch::Tensor giant);
 // hmc.hip
 int64_t hmc_workspace();
 void hmc_leapfrog(torch::Tensor q, torch::Tensor p, torch::Tensor g, torch::Tensor inv_mass,
@@ -285,6 +292,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("lincomb", &mg::lincomb);
   m.def("lincomb_cols", &mg::lincomb_cols);
   m.def("compact_diag", &mg::compact_diag);
+  m.def("weighted_gram", &mg::weighted_gram);
+  m.def("smf_jacobian_lanes", &mg::smf_jacobian_lanes);
   m.def("hmc_workspace", &mg::hmc_workspace);
   m.def("hmc_leapfrog", &mg::hmc_leapfrog);
   m.def("hmc_momentum", &mg::hmc_momentum);

@@ -560,6 +560,13 @@ class OnePointModel(_OptimizerFrontEnds):
         ``K = 10``), reverse is faster even at ``ndim = 8`` (1.4 ms against 2.7 ms) and far
         faster at ``ndim = 64``, because every forward column reruns the hook's own torch
         ops: pass ``mode="reverse"`` where speed matters and the graph fits.
+        ``mode="native"``: the model's own
+        ``calc_partial_sumstats_and_jacobian_from_params(params, randkey=None) -> (partial,
+        jac)`` hook (optionally ``(partial, jac, sumstats_aux)``), for models that can write
+        every row of their Jacobian in one pass
+        (:class:`~multigrad_amd.models.population.PopulationSMFModel`); the base class does
+        not define it, and ``mode="native"`` on a model without it raises ``ValueError``.
+        ``mode="auto"`` uses the hook first when the model defines one.
 
         Aux and ``randkey`` are handled as in the gradient; the sumstats aux is not returned.
         """
@@ -568,10 +575,21 @@ class OnePointModel(_OptimizerFrontEnds):
 
     def _sumstats_jacobian(self, params, randkey=None, mode="auto"):
         """``(total, jac, sumstats_aux, mode_used)``; one all-reduce."""
-        if mode not in ("auto", "forward", "reverse"):
-            raise ValueError(f"mode must be 'auto', 'forward' or 'reverse', got {mode!r}")
+        if mode not in ("auto", "forward", "reverse", "native"):
+            raise ValueError("mode must be 'auto', 'forward', 'reverse' or 'native', "
+                             f"got {mode!r}")
         p = self._params(params).detach()
+        hook = getattr(self, "calc_partial_sumstats_and_jacobian_from_params", None)
+        if mode == "native" and hook is None:
+            raise ValueError("mode='native' needs the model to define "
+                             "calc_partial_sumstats_and_jacobian_from_params")
         used = "reverse" if mode == "reverse" else "forward"
+        if hook is not None and mode in ("auto", "native"):
+            used = "native"
+            with torch.no_grad():
+                out = hook(p, **_rk(randkey))
+            partial, jac = torch.as_tensor(out[0]).detach(), torch.as_tensor(out[1]).detach()
+            saux = detach_tree(out[2]) if len(out) > 2 else None
         if used == "forward":
             try:
                 partial, jac, saux = self._local_jacobian_forward(p, randkey)
@@ -584,6 +602,10 @@ class OnePointModel(_OptimizerFrontEnds):
         if used == "reverse":
             partial, jac, saux = self._local_jacobian_reverse(p, randkey)
         k = partial.numel()
+        if self.comm is None or self.comm.size == 1:
+            # nothing to reduce: no packed copy of the K * ndim Jacobian
+            jac = jac.detach().to(partial.dtype).reshape(partial.shape + (p.numel(),))
+            return partial.detach(), jac, saux, used
         packed = self._allreduce(torch.cat([partial.reshape(-1),
                                             jac.reshape(-1).to(partial.dtype)]))
         total = packed[:k].reshape(partial.shape)
@@ -667,6 +689,35 @@ class OnePointModel(_OptimizerFrontEnds):
         every rank; no collective beyond the Jacobian's."""
         return self._gauss_newton(params, randkey, mode, psd)[:3]
 
+    def calc_gauss_newton_factors_from_params(self, params, randkey=None, mode: str = "auto",
+                                              psd: bool = True):
+        """``(loss, grad, J, H)`` at ``params``: the factors of the Gauss-Newton matrix
+        ``J^T H J`` instead of the matrix.  ``J`` is the ``[K, ndim]`` sumstat Jacobian
+        (flattened sumstats; the parameters' dtype and device, ``mode`` as in
+        :meth:`calc_sumstats_jacobian_from_params`), ``H`` the symmetrised float64 ``[K, K]``
+        Hessian of the loss hook on the host (negative eigenvalues set to zero with
+        ``psd=True``) and ``grad = J^T dl/dS`` in the parameters' shape and dtype.  Nothing
+        of size ``ndim x ndim`` is formed, so this works at any parameter count; ``J`` is
+        ``K * ndim`` values (400 MB at ``K = 10`` and 1e7 float32 parameters).  Identical on
+        every rank; no collective beyond the Jacobian's."""
+        loss_out, c, J, H, _ = self._gauss_newton_factors(params, randkey, mode, psd)
+        p = self._params(params)
+        grad = (c.to(J.dtype) @ J).reshape(p.shape) if J.numel() else torch.zeros_like(p)
+        return loss_out, grad, J, H
+
+    def _gauss_newton_factors(self, params, randkey=None, mode="auto", psd=True):
+        """``(loss, c, J, H, mode_used)``: ``c = dl/dS`` ``[K]`` on the parameters' device,
+        ``J`` ``[K, ndim]`` in the parameters' dtype, ``H`` ``[K, K]`` float64 on the host."""
+        total, jac, saux, used = self._sumstats_jacobian(params, randkey, mode)
+        loss_out, gs, hess = self._loss_derivatives(total, saux, randkey)
+        p = self._params(params)
+        J = jac.reshape(total.numel(), -1).to(p.dtype)
+        hess = hess.double().cpu()   # K is small: the eigendecomposition runs on the host
+        if psd and hess.numel() and bool(torch.isfinite(hess).all()):
+            lam, vec = torch.linalg.eigh(hess)
+            hess = (vec * lam.clamp_min(0.0)) @ vec.T
+        return loss_out, gs, J, hess, used
+
     def _gauss_newton(self, params, randkey=None, mode="auto", psd=True):
         total, jac, saux, used = self._sumstats_jacobian(params, randkey, mode)
         loss_out, gs, hess = self._loss_derivatives(total, saux, randkey)
@@ -697,20 +748,37 @@ class OnePointModel(_OptimizerFrontEnds):
 
     def run_gauss_newton(self, guess, maxsteps: int = 50, randkey=None, damping: float = 1e-3,
                          ftol: float = 2.2e-9, gtol: float = 1e-8, mode: str = "auto",
-                         param_bounds=None):
+                         param_bounds=None, solver: str = "auto"):
         """Damped Gauss-Newton (Levenberg-Marquardt) fit from ``guess``; returns a
         ``scipy.optimize.OptimizeResult`` on every rank
         (:func:`multigrad_amd.optim.gauss_newton.run_gauss_newton`).  Each iteration takes one
         sumstat Jacobian (``mode`` as in :meth:`calc_sumstats_jacobian_from_params`) and one
         loss evaluation per trial step; ``randkey`` is held constant.  Parameter bounds are
-        not offered."""
+        not offered.
+
+        ``solver="dense"`` forms the ``[ndim, ndim]`` Gauss-Newton matrix and solves on the
+        host (thousands of parameters at most).  ``solver="dual"`` solves the same damped
+        system through its ``K x K`` dual
+        (:func:`multigrad_amd.optim.gauss_newton.run_gauss_newton_dual`): every
+        ``ndim``-sized vector stays on the parameters' device, ``res.x`` and ``res.jac`` are
+        tensors there, ``res.hess_inv`` is an operator and ``res.solver == "dual"``; it holds
+        the ``K * ndim`` Jacobian (400 MB at ``K = 10`` and 1e7 float32 parameters) and works
+        at any parameter count.  ``solver="auto"`` (default) picks the dual form only for
+        ``ndim > 8192``, where the dense float64 matrix passes 0.5 GB."""
         from ..optim import gauss_newton as _gn
         if param_bounds is not None:
             raise ValueError("run_gauss_newton does not offer parameter bounds; use run_bfgs "
                              "or run_adam for a bounded fit")
+        if solver not in ("auto", "dense", "dual"):
+            raise ValueError(f"solver must be 'auto', 'dense' or 'dual', got {solver!r}")
         key = None if randkey is None else (
             randkey if hasattr(randkey, "split") else init_randkey(randkey))
         x0 = as_param_tensor(guess, device=self.param_device(), dtype=self.dtype)
+        if solver == "dual" or (solver == "auto" and x0.numel() > 8192):
+            return _gn.run_gauss_newton_dual(
+                lambda x: self._gauss_newton_factors(x, key, mode, True),
+                lambda x: self.calc_loss_from_params(x, randkey=key),
+                x0, maxsteps=maxsteps, damping=damping, ftol=ftol, gtol=gtol, comm=self.comm)
         return _gn.run_gauss_newton(
             lambda x: self._gauss_newton(x, key, mode, True),
             lambda x: self.calc_loss_from_params(x, randkey=key),

@@ -27,7 +27,7 @@ import torch
 
 from ..ops.smf import (PopulationShard, SmfBins, logmse_loss, prepare_forward, smf_edge_weights_into,
                        smf_forward_into, smf_forward_slab, smf_slab_reduce, smf_sumstats,
-                       smf_vjp_adam_into, smf_vjp_into)
+                       smf_sumstats_and_jacobian, smf_vjp_adam_into, smf_vjp_into)
 from ..parallel.comm import get_world_comm
 from .onepoint import OnePointModel
 
@@ -298,6 +298,15 @@ class PopulationSMFModel(OnePointModel):
 
     def calc_partial_sumstats_from_params(self, params, randkey=None):
         return smf_sumstats(torch.as_tensor(params).reshape(-1), self.shard, self.bins, True)
+
+    def calc_partial_sumstats_and_jacobian_from_params(self, params, randkey=None):
+        """``(partial, jac)``: this rank's partial sumstats and their ``[nb, nparams]``
+        Jacobian from one residual forward and one pass over the residuals
+        (:func:`~multigrad_amd.ops.smf.smf_sumstats_and_jacobian`): the native mode of
+        :meth:`~multigrad_amd.models.onepoint.OnePointModel.calc_sumstats_jacobian_from_params`.
+        The Jacobian is ``nb * nparams`` values (400 MB at the headline size)."""
+        return smf_sumstats_and_jacobian(torch.as_tensor(params).reshape(-1), self.shard,
+                                         self.bins, True)
 
     def calc_loss_from_sumstats(self, sumstats, sumstats_aux=None, randkey=None):
         t = self.aux_data["target_sumstats"]

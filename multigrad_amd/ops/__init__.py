@@ -3,7 +3,8 @@ from ._ext import available, ext
 
 __all__ = ["available", "ext", "gaussian_binned_sum", "gaussian_binned_sum_2d",
            "gaussian_binned_sum_multi", "gaussian_binned_sum_by_group",
-           "gaussian_binned_sum_fine", "FineBins", "GroupIndex", "group_gather", "segment_sum"]
+           "gaussian_binned_sum_fine", "FineBins", "GroupIndex", "group_gather", "segment_sum",
+           "weighted_gram"]
 
 
 def __getattr__(name):  # lazy: importing the package loads no op module and no device
@@ -25,4 +26,7 @@ def __getattr__(name):  # lazy: importing the package loads no op module and no 
     if name in ("GroupIndex", "group_gather", "segment_sum"):
         from . import groups
         return getattr(groups, name)
+    if name == "weighted_gram":
+        from .gram import weighted_gram
+        return weighted_gram
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

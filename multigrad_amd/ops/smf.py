@@ -18,6 +18,7 @@ from ._ext import ext
 from ..utils.trace import trace
 
 __all__ = ["SmfBins", "PopulationShard", "smf_sumstats", "smf_sumstats_reference",
+           "smf_jacobian_into", "smf_sumstats_and_jacobian",
            "logmse_loss", "normal_cdf", "TILE_HALOS", "TILE_POPS"]
 
 TILE_HALOS = 2048
@@ -754,6 +755,107 @@ def smf_edge_weights_into(g: torch.Tensor, bins: SmfBins, h: torch.Tensor) -> to
         return h
     ext().smf_edge_weights(g, list(bins.edges), list(bins.scale), h)
     return h
+
+
+def _unit_edge_weights(bins: SmfBins, device) -> torch.Tensor:
+    """``[nb, nbp + 1]`` float32: row k holds the edge weights of the unit cotangent ``e_k``
+    (:func:`smf_edge_weights_into`): ``h_k = -scale_k / sqrt(2 pi)``, ``h_{k+1} = +scale_k /
+    sqrt(2 pi)``."""
+    h = torch.zeros(bins.nb, bins.nbp + 1, dtype=torch.float64)
+    c = torch.as_tensor(bins.scale, dtype=torch.float64) / math.sqrt(2 * math.pi)
+    k = torch.arange(bins.nb)
+    h[k, k] = -c
+    h[k, k + 1] = c
+    return h.to(device=device, dtype=torch.float32)
+
+
+def smf_jacobian_into(theta: torch.Tensor, shard: PopulationShard, bins: SmfBins, log_sigma: bool,
+                      jac: torch.Tensor, chunk: Optional[int] = None,
+                      residuals_ready: bool = False, order: str = "user") -> torch.Tensor:
+    """Jacobian of this rank's partial sumstats into ``jac`` (``[nb, theta.numel()]``
+    float32, contiguous): row k is ``dS_k / dtheta`` of the shard, in ``theta``'s order.
+    With ``chunk`` set only that chunk's columns are written, as in :func:`smf_vjp_into`.
+
+    Lanes layout with residuals (``not shard.vjp_recompute``): ONE pass over the residuals
+    of a forward at the same ``theta`` writes all ``nb`` rows (``csrc/smf_jacobian.hip``),
+    where ``nb`` VJPs read them ``nb`` times.  ``residuals_ready`` as in
+    :func:`smf_vjp_into`: unless it is set and the shard holds residuals, the residual
+    forward runs here first.  Every other device case (``lane_order="local"``, the tiles
+    layout, shared-parameter shards) runs ``nb`` VJPs with the edge weights of the unit
+    cotangents, one row each.  CPU: rows by float64 autograd of the PyTorch reference over
+    the chunk's halos.
+
+    ``jac`` holds ``nb * P`` floats (400 MB at 10 bins and 1e7 parameters, 4 GB at 1e8);
+    there is no streaming variant."""
+    if order == "internal" and shard.layout != "lanes":
+        raise ValueError("internal parameter order needs the lanes layout")
+    nb = bins.nb
+    P = theta.numel()
+    if jac.dim() != 2 or tuple(jac.shape) != (nb, P) or not jac.is_contiguous():
+        raise ValueError(f"jac must be a contiguous [{nb}, {P}] tensor, got {tuple(jac.shape)}")
+    if theta.device.type != "cuda":
+        h0, h1 = shard.halo_range(chunk)
+        p0, p1 = (0, shard.npop) if chunk is None else (shard.chunk_pops[chunk], shard.chunk_pops[chunk + 1])
+        th = _user_theta(theta.detach(), shard, order)
+        th = th.reshape(-1)[:2 * shard.npop].double().clone().requires_grad_(True)
+        xs = shard.x[h0:h1].double()
+        ps = None if shard.pop is None else shard.pop[h0:h1]
+        with torch.enable_grad():
+            S = smf_sumstats_reference(th, xs, ps, bins, log_sigma)
+            for k in range(nb):
+                (g,) = torch.autograd.grad(S[k], th, retain_graph=True, allow_unused=True)
+                if g is None:
+                    g = torch.zeros_like(th)
+                if order == "internal":
+                    g = g.reshape(-1, 2)[shard.perm].reshape(-1)
+                jac[k, 2 * p0:2 * p1] = g[2 * p0:2 * p1].to(jac.dtype)
+        return jac
+    if jac.dtype != torch.float32 or theta.dtype != torch.float32:
+        raise ValueError("the device Jacobian takes float32 theta and jac")
+    if shard.layout == "lanes" and not shard.vjp_recompute:
+        if not residuals_ready or shard.resid is None:
+            nblk = shard.fwd_rows(1, nb, log_sigma, bins.rel_tail, chunk, resid=True)
+            slab = torch.empty(nblk * bins.nbp, dtype=torch.float32, device=theta.device)
+            smf_forward_slab(theta, shard, bins, log_sigma, slab, chunk, resid=True, order=order)
+        g0, g1 = shard.group_range(chunk)
+        k0, k1 = (0, shard.giant.shape[0]) if chunk is None else \
+            (shard.chunk_giant[chunk], shard.chunk_giant[chunk + 1])
+        giant = shard.giant_int if order == "internal" else shard.giant
+        # part indices are global to the shard: shard.partials has one float2 per part
+        nparts = shard.partials.numel() // 2 if shard.giant.shape[0] else 0
+        parts = torch.empty(max(2 * nb * nparts, 1), dtype=torch.float32, device=theta.device)
+        ext().smf_jacobian_lanes(shard.slot_index(order), shard.slot_part, theta,
+                                 shard.resid_buffer(bins.nbp), 64 * g0, 64 * g1, list(bins.scale),
+                                 bool(log_sigma), jac, parts, nparts, giant[k0:k1])
+        return jac
+    hs = _unit_edge_weights(bins, theta.device)
+    for k in range(nb):
+        smf_vjp_into(theta, shard, bins, log_sigma, hs[k], jac[k], chunk=chunk,
+                     residuals_ready=residuals_ready or k > 0, order=order,
+                     recompute=shard.vjp_recompute)
+    return jac
+
+
+def smf_sumstats_and_jacobian(theta: torch.Tensor, shard: PopulationShard, bins: SmfBins,
+                              log_sigma: bool = True):
+    """``(S[nb], jac[nb, P])`` of this rank's shard at ``theta`` (interleaved ``(a, s)`` per
+    population, user order): one residual forward plus the Jacobian pass of
+    :func:`smf_jacobian_into`.  No autograd; both outputs have ``theta``'s dtype (the device
+    kernels work in float32).  ``jac`` is ``nb * P`` values: see :func:`smf_jacobian_into`."""
+    th = theta.detach().reshape(-1)
+    if th.device.type != "cuda":
+        jac = torch.zeros(bins.nb, th.numel(), dtype=torch.float64)
+        smf_jacobian_into(th, shard, bins, log_sigma, jac)
+        with torch.no_grad():
+            S = smf_sumstats_reference(th, shard.x, shard.pop, bins, log_sigma)
+        return S, jac.to(th.dtype)
+    t32 = th.to(torch.float32).contiguous()
+    out = torch.empty(bins.nbp, dtype=torch.float32, device=th.device)
+    resid = shard.layout == "lanes" and not shard.vjp_recompute
+    smf_forward_into(t32, shard, bins, log_sigma, out, resid=resid)
+    jac = torch.empty(bins.nb, t32.numel(), dtype=torch.float32, device=th.device)
+    smf_jacobian_into(t32, shard, bins, log_sigma, jac, residuals_ready=resid)
+    return out[:bins.nb].to(th.dtype), jac.to(th.dtype)
 
 
 class _SmfSumstats(torch.autograd.Function):
