@@ -45,6 +45,7 @@ import torch
 
 from ..ops.hmc import hmc_commit_, hmc_leapfrog_, hmc_momentum_, hmc_workspace
 from ..utils.random import PRNGKey, init_randkey
+from ._quasi_newton import driver, finish
 from ._reduce import DeviceReducer
 
 __all__ = ["hmc_sample", "run_hmc", "KeyNoise", "HMCResult", "warmup_windows", "DualAveraging"]
@@ -156,11 +157,12 @@ def _local_track(layout, track: torch.Tensor, P: int, device) -> torch.Tensor:
     return pos[track + 1].contiguous()
 
 
-def _hmc_sample_impl(obj, nsamples: int = 1000, warmup: int = 500, nleapfrog: int = 10,
-                     step_size: float = 0.1, loss_scale: float = 1.0, jitter: float = 0.0,
-                     seed=0, noise=None, target_accept: float = 0.8, adapt_step_size: bool = True,
-                     adapt_mass: bool = True, inv_mass=None, history: str = "full",
-                     track=None) -> HMCResult:
+@driver(single_thread_blas=False)
+def hmc_sample(obj, nsamples: int = 1000, warmup: int = 500, nleapfrog: int = 10,
+               step_size: float = 0.1, loss_scale: float = 1.0, jitter: float = 0.0,
+               seed=0, noise=None, target_accept: float = 0.8, adapt_step_size: bool = True,
+               adapt_mass: bool = True, inv_mass=None, history: str = "full",
+               track=None) -> HMCResult:
     """Sample ``exp(-loss_scale * loss)`` over ``obj`` (the objective interface of the device
     L-BFGS: :class:`~multigrad_amd.optim.lbfgs.GenericObjective`, the engine objective) by
     HMC; see the module docstring for the algorithm.
@@ -348,16 +350,11 @@ def _hmc_sample_impl(obj, nsamples: int = 1000, warmup: int = 500, nleapfrog: in
             hooks(t, U, None, (lambda: q) if not sharded else None)
     if hasattr(bar, "close"):
         bar.close()
-    red.check("HMC")
-    if getattr(obj, "check", None) is not None:
-        obj.check("HMC")  # the objective's own exchanges (engine: ZeRO two-shot, one-shot)
+    xf = finish(obj, red, q, "HMC")
     # ---------------------------------------------------------------- results, user order
     var = m2 / max(nsamples - 1, 1)
     if tracked is not None and not identity and sharded and comm is not None and comm.size > 1:
         comm.all_reduce(tracked)  # the owner's values; zeros elsewhere
-    xf = obj.full(q)
-    if getattr(obj, "finalize", None) is not None:
-        xf = obj.finalize(q)
     rate = n_acc / nsamples if nsamples else (n_acc_warm / warmup if warmup else 0.0)
     return HMCResult(
         samples=layout.from_local(samples) if keep_full else None, tracked=tracked,
@@ -365,17 +362,6 @@ def _hmc_sample_impl(obj, nsamples: int = 1000, warmup: int = 500, nleapfrog: in
         accept_rate=rate, step_size=eps,
         inv_mass=im if im.numel() == 1 else layout.from_local(im), n_divergent=n_div, n_divergent_warmup=n_div_warm, nfev=nfev,
         warmup_windows=windows, reduction=red.describe())
-
-
-def hmc_sample(*args, **kwargs) -> HMCResult:
-    """See ``_hmc_sample_impl``; runs inside the drivers' fail-fast guard."""
-    from ..utils.hooks import driver_guard
-    obj = args[0] if args else kwargs.get("obj")
-    with driver_guard(getattr(obj, "comm", None)):
-        return _hmc_sample_impl(*args, **kwargs)
-
-
-hmc_sample.__doc__ = _hmc_sample_impl.__doc__
 
 
 def run_hmc(loss_and_grad_fn: Callable, params, nsamples: int = 1000, warmup: int = 500,

@@ -75,8 +75,9 @@ class DeviceLbfgsInvHessProduct(LinearOperator):
 
     ``HS`` is the history ring ``[>= 2 R, n_local]`` (rows ``0..R-1`` the ``s`` slots, rows
     ``R..2R-1`` the ``y`` slots), ``order`` the accepted slots oldest first, ``SY`` / ``YY``
-    the ``R x R`` global inner products by slot (``SS``, where the optimizer keeps it, is only
-    held: no method reads it yet; it is what the direct form ``B = H^-1`` would need), ``red``
+    the ``R x R`` global inner products by slot (``SS``, which both optimizers hand over with
+    their :class:`~multigrad_amd.optim._quasi_newton.PairRing`, is only held: no method reads
+    it yet; it is what the direct form ``B = H^-1`` would need), ``red``
     the optimizer's :class:`~multigrad_amd.optim._reduce.DeviceReducer`, ``layout`` the
     objective's ``vector_layout()`` and ``jac`` the local ``dx/du`` (transform mode)."""
 
@@ -266,8 +267,10 @@ def check_hess_inv_objective(obj) -> None:
         _layout_of(obj)
 
 
-def build_hess_inv(obj, HS, R, order, SY, YY, red, x, SS=None, dot=None):
-    """The operator for an optimizer's final state (``x``: its final local vector)."""
+def build_hess_inv(obj, ring, red, x, dot=None):
+    """The operator for an optimizer's final state (``ring``: its
+    :class:`~multigrad_amd.optim._quasi_newton.PairRing`, ``x``: its final local vector)."""
+    HS, R, order = ring.HS, ring.R, ring.order
     layout = _layout_of(obj)
     bounds = getattr(obj, "bounds", None)
     jac = bounds.dpdu(x).to(torch.float32).contiguous() if bounds is not None else None
@@ -276,4 +279,5 @@ def build_hess_inv(obj, HS, R, order, SY, YY, red, x, SS=None, dot=None):
     for q in set(range(R)) - set(order):
         HS[q].zero_()
         HS[R + q].zero_()
-    return DeviceLbfgsInvHessProduct(HS, R, order, SY, YY, red, layout, SS=SS, jac=jac, dot=dot)
+    return DeviceLbfgsInvHessProduct(HS, R, order, ring.SY, ring.YY, red, layout, SS=ring.SS,
+                                     jac=jac, dot=dot)

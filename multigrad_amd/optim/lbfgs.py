@@ -18,6 +18,10 @@ optimizer itself must live on the GPUs, so this is an SPMD L-BFGS:
   decides on loss values and directional derivatives that are bitwise identical on all
   ranks (all-reduced), so every rank takes the same decisions without broadcasts.
 
+The history ring, the line search and the frame of the driver are shared with L-BFGS-B
+(:mod:`multigrad_amd.optim._quasi_newton`); this module keeps the compact inverse-Hessian
+product and the phases of one iteration: direction, search, update.
+
 Termination follows scipy's L-BFGS-B: ``(f_k - f_{k+1}) / max(|f_k|, |f_{k+1}|, 1) <= ftol``
 or ``max|g| <= gtol`` or ``maxiter``.  Box bounds are supported through the same
 bijective transforms as Adam (:mod:`multigrad_amd.optim.transforms`); the exact scipy
@@ -26,7 +30,6 @@ L-BFGS-B projection semantics remain available through :func:`multigrad_amd.opti
 from __future__ import annotations
 
 import math
-import os
 from typing import Callable
 
 import numpy as np
@@ -34,7 +37,8 @@ import scipy.linalg
 import scipy.optimize
 import torch
 
-from ..ops.lbfgs import MultiDot, lincomb_
+from ..ops.lbfgs import MultiDot
+from ._quasi_newton import HostCollectives, PairRing, Run, best_decrease, driver, strong_wolfe
 from ._reduce import DeviceReducer
 
 __all__ = ["lbfgs_minimize", "GenericObjective", "run_lbfgs_device"]
@@ -81,20 +85,93 @@ class GenericObjective:
         return float(torch.as_tensor(loss).detach().double()), g.contiguous()
 
 
-def _cubic_min(a, fa, da, b, fb, db):
-    """Minimiser of the cubic interpolating (a, fa, da), (b, fb, db) (None if degenerate)."""
-    d1 = da + db - 3 * (fa - fb) / (a - b)
-    disc = d1 * d1 - da * db
-    if disc < 0 or not np.isfinite(disc):
-        return None
-    d2 = math.copysign(math.sqrt(disc), b - a)
-    den = db - da + 2 * d2
-    if den == 0:
-        return None
-    return b - (b - a) * (db + d2 - d1) / den
+def _absmax(gv: torch.Tensor) -> torch.Tensor:
+    return gv.abs().max().double() if gv.numel() else torch.zeros((), dtype=torch.float64,
+                                                                 device=gv.device)
 
 
-def _lbfgs_minimize_impl(obj, maxiter: int = 100, m: int = 10, ftol: float = 1e7 * _EPS,
+class _Run(Run):
+    """A run of the unbounded driver.  The current gradient lives in the row behind the ring
+    (``HX[2R]``): one multi-dot of all rows against (s_new, y_new, g) gives every scalar an
+    iteration needs (s.y, y.y, the new Gram rows, S^T g, Y^T g, g.g), and max|g| rides along in
+    the same reduction and device->host copy: with the line search's one copy per
+    evaluation, a typical iteration makes two."""
+
+    def __init__(self, obj, red, m: int):
+        n, dev = obj.n_local, obj.device
+        super().__init__(obj, red, PairRing(m, n, dev, extra_rows=1), "L-BFGS")
+        R = self.ring.R
+        self.g_row = self.ring.HX[2 * R]
+        self.dot = MultiDot(2 * R + 1, n, dev)
+        self.dot1 = MultiDot(1, n, dev)
+        self.Sg = np.zeros(R)
+        self.Yg = np.zeros(R)
+        self.x = obj.x0().contiguous()
+        self.f, self.g = self.trial.initial(self.x)
+        self.d = torch.empty_like(self.x)
+        # (global g.g, global max|g|) in one copy
+        h = red.reduce(sums=[self.dot1(self.g.view(1, -1), 1, [self.g])], maxes=[_absmax(self.g)])
+        self.gg, self.gmax = float(h[0]), float(h[1])
+
+
+def _direction(st: _Run):
+    """Write the search direction ``st.d`` (compact inverse-Hessian product); returns
+    ``(g.d, first trial step)``.  g.d follows from the host copies of S^T g, Y^T g and g.g (no
+    device round trip)."""
+    ring = st.ring
+    R, order = ring.R, ring.order
+    gd = -st.gg
+    if order:
+        idx = np.array(order)
+        gamma, a, b = compact_coefficients(ring.SY, ring.YY, st.Sg, st.Yg, order)
+        cvec = np.zeros(2 * R)
+        cvec[idx] = -a
+        cvec[R + idx] = -gamma * b
+        ring.lincomb(cvec, -gamma, st.g, st.d)
+        gd = -gamma * st.gg - float(a @ st.Sg[idx]) - gamma * float(b @ st.Yg[idx])
+    else:
+        st.d.copy_(-st.g)
+    if not np.isfinite(gd) or gd >= 0:  # not a descent direction: reset memory
+        order.clear()
+        st.d.copy_(-st.g)
+        gd = -st.gg
+    return gd, (1.0 if order else min(1.0, 1.0 / math.sqrt(max(-gd, 1e-300))))
+
+
+def _search(st: _Run, gd: float, a1: float, c1: float, c2: float, maxls: int):
+    """Strong-Wolfe step along ``st.d``, else the best decrease seen, else None.  The local
+    d.g of a trial point goes into the one reduction of its evaluation."""
+    dot1, d = st.dot1, st.d
+    st.trial.start(st.x, d, lambda ga, first: [dot1(ga.view(1, -1), 1, [d])])
+    best = strong_wolfe(st.trial, st.f, gd, a1, c1, c2, maxls)
+    return best_decrease(best, st.trial.cache, st.f)
+
+
+def _update(st: _Run, best: float) -> None:
+    """Move to the accepted trial point; the new pair goes into the spare slot and is
+    measured there (the one dot block of the iteration)."""
+    ring = st.ring
+    R = ring.R
+    f_new, g_new, _ = st.trial.cache[best]
+    q = ring.spare()
+    s_vec, y_vec = ring.s(q), ring.y(q)
+    torch.mul(st.d, best, out=s_vec)
+    st.x.add_(s_vec)
+    torch.sub(g_new, st.g, out=y_vec)
+    st.g_row.copy_(g_new)
+    dv = st.dot(ring.HX, 2 * R + 1, [s_vec, y_vec, st.g_row])  # (2R+1, 3)
+    host = st.red.reduce(sums=[dv], maxes=[_absmax(g_new)])
+    dots = host[:-1].reshape(2 * R + 1, 3)
+    st.gmax = float(host[-1])
+    st.gg = float(dots[2 * R, 2])
+    ring.accept(q, dots)
+    st.Sg[:] = dots[:R, 2]
+    st.Yg[:] = dots[R:2 * R, 2]
+    st.f, st.g = f_new, g_new
+
+
+@driver(single_thread_blas=True)
+def lbfgs_minimize(obj, maxiter: int = 100, m: int = 10, ftol: float = 1e7 * _EPS,
                    gtol: float = 1e-5, maxls: int = 20, c1: float = 1e-4, c2: float = 0.9,
                    callback=None, hess_inv: bool = True) -> scipy.optimize.OptimizeResult:
     """Minimise ``obj`` (see :class:`GenericObjective`) with L-BFGS; SPMD-consistent.
@@ -112,178 +189,34 @@ def _lbfgs_minimize_impl(obj, maxiter: int = 100, m: int = 10, ftol: float = 1e7
     if hess_inv:
         from .invhess import check_hess_inv_objective
         check_hess_inv_objective(obj)
-    comm, sharded = obj.comm, obj.sharded
-    n = obj.n_local
-    dev = obj.device
     if not 1 <= int(m) <= 120:
         # 2 (m + 1) history rows go through one lincomb launch (csrc/lbfgs.hip: <= 256 rows)
         raise ValueError(f"L-BFGS history m must be in 1..120, got {m}")
-    red = DeviceReducer(comm, sharded, dev)  # collective (may connect peer memory)
-    x = obj.x0().contiguous()
-    f, g = obj(x)
-    g = g.clone()  # the objective may return a view of a buffer the next evaluation reuses
-    nfev = 1
-    # A ring of R = m + 1 pair slots: rows 0..R-1 hold s, rows R..2R-1 hold y, row 2R the
-    # current gradient.  The new pair is written straight into the spare slot (no copy when
-    # it is accepted); one multi-dot of all rows against (s_new, y_new, g) gives every scalar
-    # an iteration needs (s.y, y.y, the new Gram rows, S^T g, Y^T g, g.g), and max|g| rides
-    # along in the same reduction and device->host copy: with the line search's one copy per
-    # evaluation, a typical iteration makes two.
-    R = m + 1
-    HX = torch.zeros((2 * R + 1, n), dtype=torch.float32, device=dev)
-    HS = HX[:2 * R]
-    g_row = HX[2 * R]
-    dot = MultiDot(2 * R + 1, n, dev)
-    dot1 = MultiDot(1, n, dev)
-    SY = np.zeros((R, R))
-    YY = np.zeros((R, R))
-    Sg = np.zeros(R)
-    Yg = np.zeros(R)
-    order: list = []  # accepted slots, oldest -> newest (at most m)
-    d = torch.empty_like(x)
-    xt = torch.empty_like(x)
-    dev_call = getattr(obj, "device_call", None) if dev.type == "cuda" else None
-    coef = torch.zeros(2 * R, dtype=torch.float32, device=dev)
-
-    def absmax(gv: torch.Tensor) -> torch.Tensor:
-        return gv.abs().max().double() if gv.numel() else torch.zeros((), dtype=torch.float64,
-                                                                     device=gv.device)
-
-    def gstats(gv: torch.Tensor):
-        """(global g.g, global max|g|) in one copy."""
-        h = red.reduce(sums=[dot1(gv.view(1, -1), 1, [gv])], maxes=[absmax(gv)])
-        return float(h[0]), float(h[1])
-
-    status, message = 1, "STOP: TOTAL NO. of ITERATIONS REACHED LIMIT"
-    nit = 0
-    from ..utils.hooks import StepHooks
-    hooks = StepHooks(comm, what="L-BFGS iterate")  # MULTIGRAD_CHECK_EVERY / _METRICS
-    gg, gmax = gstats(g)
-    host0 = getattr(comm, "host_collectives", 0) if comm is not None else 0
-    if gmax <= gtol:
-        status, message = 0, "CONVERGENCE: NORM_OF_PROJECTED_GRADIENT_<=_PGTOL"
+    red = DeviceReducer(obj.comm, obj.sharded, obj.device)  # collective (may connect peer memory)
+    st = _Run(obj, red, m)
+    host = HostCollectives(obj.comm)
+    if st.gmax <= gtol:
+        st.converged_gradient()
     else:
         for k in range(maxiter):
-            # ---------------- search direction (compact inverse-Hessian product); g.d
-            # follows from the host copies of S^T g, Y^T g and g.g (no device round trip)
-            gd = -gg
-            if order:
-                idx = np.array(order)
-                gamma, a, b = compact_coefficients(SY, YY, Sg, Yg, order)
-                cvec = np.zeros(2 * R)
-                cvec[idx] = -a
-                cvec[R + idx] = -gamma * b
-                coef.copy_(torch.from_numpy(cvec.astype(np.float32)))
-                lincomb_(HS, 2 * R, coef, -gamma, g, d)
-                gd = -gamma * gg - float(a @ Sg[idx]) - gamma * float(b @ Yg[idx])
-            else:
-                d.copy_(-g)
-            if not np.isfinite(gd) or gd >= 0:  # not a descent direction: reset memory
-                order.clear()
-                d.copy_(-g)
-                gd = -gg
-            a1 = 1.0 if order else min(1.0, 1.0 / math.sqrt(max(-gd, 1e-300)))
-            # ---------------- strong-Wolfe line search
-            cache = {}
-
-            def phi(alpha):
-                nonlocal nfev
-                torch.add(x, d, alpha=float(alpha), out=xt)
-                if dev_call is not None:
-                    # the loss (already global) and the local d.g: one reduction, one copy
-                    lt, ga = dev_call(xt)
-                    ga = ga.clone()
-                    h = red.reduce(sums=[dot1(ga.view(1, -1), 1, [d])], local=[lt.reshape(1)])
-                    da, fa = float(h[0]), float(h[1])
-                else:
-                    fa, ga = obj(xt)
-                    ga = ga.clone()
-                    da = float(red.reduce(sums=[dot1(ga.view(1, -1), 1, [d])])[0])
-                nfev += 1
-                cache[alpha] = (fa, ga, da)
-                return fa, da
-
-            f0, d0 = f, gd
-            a_prev, f_prev, dphi_prev = 0.0, f0, d0
-            alpha, best = a1, None
-            for i in range(maxls):
-                fa, da = phi(alpha)
-                if not np.isfinite(fa) or fa > f0 + c1 * alpha * d0 or (i > 0 and fa >= f_prev):
-                    best = _zoom(phi, a_prev, alpha, f_prev, fa, dphi_prev, da, f0, d0, c1, c2, maxls)
-                    break
-                if abs(da) <= -c2 * d0:
-                    best = alpha
-                    break
-                if da >= 0:
-                    best = _zoom(phi, alpha, a_prev, fa, f_prev, da, dphi_prev, f0, d0, c1, c2, maxls)
-                    break
-                a_prev, f_prev, dphi_prev = alpha, fa, da
-                alpha = alpha * 2.0
-            if best is None or best not in cache:
-                # no acceptable step: keep the best decrease seen, else stop
-                cands = [(v[0], a) for a, v in cache.items() if v[0] < f0]
-                if not cands:
-                    status, message = 2, "ABNORMAL_TERMINATION_IN_LNSRCH"
-                    break
-                best = min(cands)[1]
-            f_new, g_new, _ = cache[best]
-            # ---------------- update iterate and history (new pair in the spare slot q)
-            q = min(set(range(R)) - set(order))
-            s_vec, y_vec = HS[q], HS[R + q]
-            torch.mul(d, best, out=s_vec)
-            x.add_(s_vec)
-            torch.sub(g_new, g, out=y_vec)
-            g_row.copy_(g_new)
-            nit = k + 1
-            dv = dot(HX, 2 * R + 1, [s_vec, y_vec, g_row])  # (2R+1, 3)
-            host = red.reduce(sums=[dv], maxes=[absmax(g_new)])
-            dots = host[:-1].reshape(2 * R + 1, 3)
-            gmax = float(host[-1])
-            sy_new, yy_new = float(dots[q, 1]), float(dots[R + q, 1])
-            gg = float(dots[2 * R, 2])
-            if sy_new > _EPS * yy_new and yy_new > 0:  # accept: q joins, the oldest leaves
-                if len(order) == m:
-                    order.pop(0)
-                order.append(q)
-                for o in order:
-                    if o == q:
-                        SY[q, q] = sy_new
-                        YY[q, q] = yy_new
-                    else:
-                        SY[o, q] = dots[o, 1]          # s_o . y_new
-                        SY[q, o] = dots[R + o, 0]      # s_new . y_o
-                        YY[o, q] = YY[q, o] = dots[R + o, 1]
-            Sg[:] = dots[:R, 2]
-            Yg[:] = dots[R:2 * R, 2]
-            f_old, f, g = f, f_new, g_new
+            gd, a1 = _direction(st)
+            best = _search(st, gd, a1, c1, c2, maxls)
+            if best is None:
+                st.no_step()
+                break
+            f_old = st.f
+            _update(st, best)
+            st.nit = k + 1
             if callback is not None:
-                h0 = getattr(comm, "host_collectives", 0) if comm is not None else 0
-                callback(obj.full(x))
-                if comm is not None:  # the callback's own collectives are not the loop's
-                    host0 += getattr(comm, "host_collectives", 0) - h0
-            if hooks.active:
-                hooks(k, f, None, (lambda: x) if not sharded else None)
-            if gmax <= gtol:
-                status, message = 0, "CONVERGENCE: NORM_OF_PROJECTED_GRADIENT_<=_PGTOL"
+                host.callback(callback, obj, st.x)
+            if st.hooks.active:
+                st.hooks(k, st.f, None, (lambda: st.x) if not obj.sharded else None)
+            if st.gmax <= gtol:
+                st.converged_gradient()
                 break
-            if (f_old - f) <= ftol * max(abs(f_old), abs(f), 1.0):
-                status, message = 0, "CONVERGENCE: REL_REDUCTION_OF_F_<=_FACTR*EPSMCH"
+            if st.converged_decrease(f_old, ftol):
                 break
-    host_calls = (getattr(comm, "host_collectives", 0) - host0) if comm is not None else 0
-    red.check("L-BFGS")
-    if getattr(obj, "check", None) is not None:
-        obj.check("L-BFGS")  # the objective's own exchanges (engine: ZeRO two-shot, one-shot)
-    xf = obj.full(x)
-    if getattr(obj, "finalize", None) is not None:
-        xf = obj.finalize(x)
-    res = scipy.optimize.OptimizeResult(
-        x=xf, fun=f, jac=g, nit=nit, nfev=nfev, njev=nfev, status=status,
-        success=status == 0, message=message, host_collectives=host_calls,
-        reduction=red.describe())
-    if hess_inv:
-        from .invhess import build_hess_inv
-        res["hess_inv"] = build_hess_inv(obj, HS, R, order, SY, YY, red, x, dot=dot)
-    return res
+    return st.result(host.count, hess_inv, st.dot)
 
 
 def compact_coefficients(SY, YY, Sg, Yg, order):
@@ -303,27 +236,6 @@ def compact_coefficients(SY, YY, Sg, Yg, order):
     return gamma, a, -t
 
 
-def _zoom(phi, lo, hi, flo, fhi, dlo, dhi, f0, d0, c1, c2, maxiter):
-    for _ in range(maxiter):
-        a = _cubic_min(lo, flo, dlo, hi, fhi, dhi)
-        span = hi - lo
-        lo_b, hi_b = min(lo, hi) + 0.1 * abs(span), max(lo, hi) - 0.1 * abs(span)
-        if a is None or not (lo_b <= a <= hi_b):
-            a = 0.5 * (lo + hi)
-        fa, da = phi(a)
-        if not np.isfinite(fa) or fa > f0 + c1 * a * d0 or fa >= flo:
-            hi, fhi, dhi = a, fa, da
-        else:
-            if abs(da) <= -c2 * d0:
-                return a
-            if da * (hi - lo) >= 0:
-                hi, fhi, dhi = lo, flo, dlo
-            lo, flo, dlo = a, fa, da
-        if abs(hi - lo) < 1e-12 * max(1.0, abs(lo)):
-            break
-    return lo if lo != 0.0 else None
-
-
 def run_lbfgs_device(loss_and_grad_fn: Callable, params, maxsteps: int = 100, param_bounds=None,
                      randkey=None, comm=None, history: int = 10, **kw):
     """Device L-BFGS for a generic ``loss_and_grad_fn(params[, randkey])`` (replicated).
@@ -340,16 +252,3 @@ def run_lbfgs_device(loss_and_grad_fn: Callable, params, maxsteps: int = 100, pa
     fkw = {} if randkey is None else {"randkey": init_randkey(randkey)}
     obj = GenericObjective(loss_and_grad_fn, x0, comm=comm, bounds=bounds, **fkw)
     return lbfgs_minimize(obj, maxiter=maxsteps, m=history, **kw)
-
-
-def lbfgs_minimize(*args, **kwargs):
-    """See ``_lbfgs_minimize_impl``; runs with the BLAS pools limited to one thread (the host-side
-    compact-form solves are tiny; a spinning BLAS pool would slow the CPU evaluations)."""
-    from ..utils.hooks import driver_guard
-    from ..utils.tensors import blas_single_thread
-    obj = args[0] if args else kwargs.get("obj")
-    with driver_guard(getattr(obj, "comm", None)), blas_single_thread():
-        return _lbfgs_minimize_impl(*args, **kwargs)
-
-
-lbfgs_minimize.__doc__ = _lbfgs_minimize_impl.__doc__

@@ -27,22 +27,30 @@ The reference hands its bounds to scipy's L-BFGS-B (``multigrad/bfgs.py:83-86``)
   Cauchy-point input, (B) the subspace inner products; the first evaluation of the line
   search also carries the directional derivative at the start point.
 
+One iteration is these phases, a function each: copy A with the projected gradient
+(``_measure``), the Cauchy point (``_generalized_cauchy`` around ``_cauchy_point``), copy B
+with the subspace step (``_subspace_step``), the search (``_search``), its retry along the
+truncated step (``_truncated``) and the update (``_update``).  The pair ring, the search
+itself and the frame of the driver are shared with the unbounded L-BFGS
+(:mod:`multigrad_amd.optim._quasi_newton`).
+
 Termination as scipy: ``max|P(x-g)-x| <= pgtol`` or ``(f_k-f_{k+1})/max(|f_k|,|f_{k+1}|,1)
 <= factr * eps`` or ``maxiter``.
 """
 from __future__ import annotations
 
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import scipy.linalg
 import scipy.optimize
 import torch
 
-from ..ops.lbfgs import MultiDot, lincomb_
+from ..ops.lbfgs import MultiDot
+from ._quasi_newton import HostCollectives, PairRing, Run, best_decrease, driver, strong_wolfe
 from ._reduce import DeviceReducer
-from .lbfgs import _zoom
+from .lbfgs import GenericObjective
 
 __all__ = ["lbfgsb_minimize", "run_lbfgsb_device", "BoxObjective"]
 
@@ -50,35 +58,14 @@ _EPS = np.finfo(np.float64).eps
 _B_CAP_MULTI = 1 << 16  # breakpoints per rank and Cauchy-point batch on several ranks
 
 
-class BoxObjective:
+class BoxObjective(GenericObjective):
     """Replicated objective ``loss_and_grad_fn(x) -> (loss, grad)`` in the parameters
     themselves (no transform), for :func:`lbfgsb_minimize`."""
 
     def __init__(self, loss_and_grad_fn, x0: torch.Tensor, comm=None, **fn_kwargs):
-        self.fn, self.kw, self.comm = loss_and_grad_fn, fn_kwargs, comm
-        self.sharded = False
-        x0 = x0.detach().reshape(-1).to(torch.float32)
-        self.device, self.shape = x0.device, x0.shape
-        self._x0 = x0.clone()
-        self.n_local = x0.numel()
-
-    def x0(self):
-        return self._x0.clone()
-
-    def full(self, x):
-        return x
-
-    def vector_layout(self):
-        """The optimizer's vector is the user's parameter vector."""
-        from .invhess import IdentityLayout
-        return IdentityLayout(self.n_local)
-
-    def __call__(self, x):
-        loss, grad = self.fn(x, **self.kw)
-        if isinstance(loss, (tuple, list)):
-            loss = loss[0]
-        g = torch.as_tensor(grad).detach().reshape(-1).to(device=x.device, dtype=torch.float32)
-        return float(torch.as_tensor(loss).detach().double()), g.contiguous()
+        if "bounds" in fn_kwargs:
+            raise TypeError("BoxObjective takes no bounds=: the box is lbfgsb_minimize's lo, hi")
+        super().__init__(loss_and_grad_fn, x0, comm=comm, **fn_kwargs)
 
 
 def _box(lo, hi, n, device):
@@ -89,72 +76,194 @@ def _box(lo, hi, n, device):
     return lo.contiguous(), hi.contiguous()
 
 
-class _History:
-    """m accepted (s, y) pairs in a ring of m+1 device slots (a new pair is measured in the
-    spare slot before it is accepted), with their inner products."""
-
-    def __init__(self, m: int, n: int, device):
-        self.m = int(m)
-        self.R = self.m + 1
-        self.HS = torch.zeros((2 * self.R, n), dtype=torch.float32, device=device)  # s_q, y_q
-        self.SY = np.zeros((self.R, self.R))  # s_i . y_j
-        self.SS = np.zeros((self.R, self.R))
-        self.YY = np.zeros((self.R, self.R))
-        self.order: list = []   # accepted slots, oldest first
-        self.theta = 1.0
-
-    def spare(self) -> int:
-        return min(set(range(self.R)) - set(self.order))
-
-    def s(self, q):
-        return self.HS[q]
-
-    def y(self, q):
-        return self.HS[self.R + q]
-
-    def accept(self, q: int, dots: np.ndarray) -> bool:
-        """dots[r] = (HS_r . s_q, HS_r . y_q) for every row r; decide and record."""
-        sy, yy = dots[q, 1], dots[self.R + q, 1]
-        if not (sy > _EPS * yy and yy > 0):
-            return False
-        for o in self.order + [q]:
-            self.SY[o, q] = dots[o, 1]
-            self.SY[q, o] = dots[self.R + o, 0]
-            self.SS[o, q] = self.SS[q, o] = dots[o, 0]
-            self.YY[o, q] = self.YY[q, o] = dots[self.R + o, 1]
-        self.order.append(q)
-        if len(self.order) > self.m:
-            self.order.pop(0)
-        self.theta = yy / sy
-        return True
-
-    def compact(self):
-        """``(idx, M, WWt)`` for the accepted pairs: ``M`` (2k x 2k) and the full Gram
-        matrix ``W W'`` of ``W = [Y, theta S]`` (rows in ``idx`` order)."""
-        idx = np.asarray(self.order, dtype=np.int64)
-        k = idx.size
-        if k == 0:
-            return idx, np.zeros((0, 0)), np.zeros((0, 0))
-        th = self.theta
-        sy = self.SY[np.ix_(idx, idx)]
-        D = np.diag(np.diag(sy))
-        Lm = np.tril(sy, -1)
-        ss = self.SS[np.ix_(idx, idx)]
-        K = np.block([[-D, Lm.T], [Lm, th * ss]])
-        M = np.linalg.inv(K)
-        yy = self.YY[np.ix_(idx, idx)]
-        ys = sy.T  # y_i . s_j
-        WWt = np.block([[yy, th * ys], [th * ys.T, th * th * ss]])
-        return idx, M, WWt
-
-    def rows(self, idx):
-        """Row indices of ``W = [Y_idx, S_idx]`` in HS and the theta factor per row."""
-        rows = np.concatenate([self.R + idx, idx]).astype(np.int64)
-        fac = np.concatenate([np.ones(idx.size), np.full(idx.size, self.theta)])
-        return rows, fac
+def _clip(v, lo, hi):
+    return torch.minimum(torch.maximum(v, lo), hi)
 
 
-def _lbfgsb_minimize_impl(obj, lo=None, hi=None, maxiter: int = 100, m: int = 10,
+def _compact(ring: PairRing):
+    """``(idx, M, WWt)`` for the accepted pairs: ``M`` (2k x 2k) and the full Gram
+    matrix ``W W'`` of ``W = [Y, theta S]`` (rows in ``idx`` order)."""
+    idx = np.asarray(ring.order, dtype=np.int64)
+    k = idx.size
+    if k == 0:
+        return idx, np.zeros((0, 0)), np.zeros((0, 0))
+    th = ring.theta
+    sy = ring.SY[np.ix_(idx, idx)]
+    D = np.diag(np.diag(sy))
+    Lm = np.tril(sy, -1)
+    ss = ring.SS[np.ix_(idx, idx)]
+    K = np.block([[-D, Lm.T], [Lm, th * ss]])
+    M = np.linalg.inv(K)
+    yy = ring.YY[np.ix_(idx, idx)]
+    ys = sy.T  # y_i . s_j
+    WWt = np.block([[yy, th * ys], [th * ys.T, th * th * ss]])
+    return idx, M, WWt
+
+
+def _rows(ring: PairRing, idx):
+    """Row indices of ``W = [Y_idx, S_idx]`` in HS and the theta factor per row."""
+    rows = np.concatenate([ring.R + idx, idx]).astype(np.int64)
+    fac = np.concatenate([np.ones(idx.size), np.full(idx.size, ring.theta)])
+    return rows, fac
+
+
+class _Run(Run):
+    """A run of L-BFGS-B: the box, the slot of the pair that waits to be measured and the
+    start slope of the line search under way."""
+
+    def __init__(self, obj, red, lo, hi, m: int, K: Optional[int]):
+        n, dev = obj.n_local, obj.device
+        super().__init__(obj, red, PairRing(m, n, dev), "L-BFGS-B")
+        self.lo, self.hi = _box(lo, hi, n, dev)
+        self.lo64, self.hi64 = self.lo.double(), self.hi.double()
+        self.x = _clip(obj.x0().contiguous(), self.lo, self.hi)
+        self.f, self.g = self.trial.initial(self.x)
+        self.dot = MultiDot(2 * self.ring.R, n, dev)
+        self.K = K
+        self.pending = None  # slot of a written, not yet measured pair
+        self.d0 = None       # slope at step 0 of the latest line search
+
+    def accept_pending(self, dots: np.ndarray) -> None:
+        self.ring.accept(self.pending, dots)
+        self.pending = None
+
+
+class _Model(NamedTuple):
+    """The quadratic model at the Cauchy point: the compact matrices, the rows of W in the
+    ring, ``c = W'(x^cp - x)`` and the Cauchy point."""
+    M: np.ndarray
+    WWt: np.ndarray
+    rows: np.ndarray
+    fac: np.ndarray
+    cvec: np.ndarray
+    xcp: torch.Tensor
+
+
+def _measure(st: _Run):
+    """Copy A: the pending pair's inner products with the history (the pair is accepted or
+    dropped here), the projected-gradient norm and every Cauchy-point input, in one
+    reduction and one device->host copy.  Returns ``(d.d, HS.d, max|P(x-g)-x|, breakpoints,
+    number of finite local breakpoints)`` for the projected steepest-descent direction d."""
+    x, g, lo, hi, ring = st.x, st.g, st.lo, st.hi, st.ring
+    R = ring.R
+    t = torch.where(g < 0, (x - hi) / g, torch.where(g > 0, (x - lo) / g,
+                                                      torch.full_like(g, math.inf)))
+    t = torch.where(torch.isnan(t), torch.full_like(t, math.inf), t)
+    free_path = t > 0
+    d = torch.where(free_path, -g, torch.zeros_like(g))
+    xd = x.double()
+    pg = (_clip(xd - g.double(), st.lo64, st.hi64) - xd).abs()
+    vecs = [d] if st.pending is None else [ring.s(st.pending), ring.y(st.pending), d]
+    dots_dev = st.dot(ring.HS, 2 * R, vecs)
+    tc = torch.where(free_path & torch.isfinite(t), t, torch.full_like(t, math.inf))
+    pg_l = pg.max().double() if g.numel() else torch.zeros((), dtype=torch.float64,
+                                                           device=g.device)
+    # one reduction and one copy: [d.d, HS.vecs (summed), max|pg| (max), #finite (local)]
+    packA = st.red.reduce(sums=[(d.double() * d.double()).sum(), dots_dev],
+                          maxes=[pg_l], local=[torch.isfinite(tc).sum()])
+    dots_np = packA[1:1 + 2 * R * len(vecs)].reshape(2 * R, len(vecs))
+    if st.pending is not None:
+        st.accept_pending(dots_np[:, :2])
+    return packA[0], dots_np[:, -1], float(packA[-2]), tc, int(packA[-1])
+
+
+def _generalized_cauchy(st: _Run, dd, Wd, tc, nfin) -> _Model:
+    """The Cauchy point ``P(x - t* g)`` of the compact model over the accepted pairs."""
+    ring = st.ring
+    idx, M, WWt = _compact(ring)
+    rows, fac = _rows(ring, idx)
+    tstar, cvec = _cauchy_point(dd, Wd[rows] * fac, M, ring.theta, tc, nfin, st.g, ring.HS,
+                                rows, fac, st.red, st.K)
+    return _Model(M, WWt, rows, fac, cvec, _clip(st.x - tstar * st.g, st.lo, st.hi))
+
+
+def _subspace_step(st: _Run, mdl: _Model) -> torch.Tensor:
+    """Copy B: the minimiser of the model over the variables free at the Cauchy point
+    (direct primal method), as a step ``du`` from the Cauchy point; its inner products come
+    back in one reduction and one device->host copy."""
+    x, g, ring, red = st.x, st.g, st.ring, st.red
+    M, WWt, rows, fac, cvec, xcp = mdl
+    R, th, dev = ring.R, ring.theta, x.device
+    free = (xcp > st.lo) & (xcp < st.hi)
+    kk2 = rows.size // 2
+    if kk2:
+        coef = np.zeros(2 * R)
+        coef[rows] = (M @ cvec) * fac
+        r = g + th * (xcp - x) - ring.lincomb(coef, 0.0, None, torch.empty_like(x))
+    else:
+        r = g + th * (xcp - x)
+    rF = torch.where(free, r, torch.zeros_like(r))
+    WtZr = st.dot(ring.HS, 2 * R, [rF])[:, 0]
+    if kk2:
+        act = torch.nonzero(~free).reshape(-1)  # a host sync: only where it is used
+        rows_d = torch.as_tensor(rows, device=dev)
+        GA = _gram(ring.HS[rows_d[:, None], act[None, :]].double())
+    else:
+        GA = torch.zeros((0, 0), dtype=torch.float64, device=dev)
+    redB = red.reduce(sums=[WtZr, GA])
+    if kk2:
+        GA_np = redB[2 * R:].reshape(kk2 * 2, kk2 * 2)
+        fw = fac[:, None] * fac[None, :]
+        GF = WWt - GA_np * fw               # Gram of W over the free rows
+        v = M @ (redB[:2 * R][rows] * fac)
+        N = np.eye(2 * kk2) - (M @ GF) / th
+        v = scipy.linalg.solve(N, v)
+        coef = np.zeros(2 * R)
+        coef[rows] = v * fac
+        zwv = ring.lincomb(coef, 0.0, None, torch.empty_like(x))
+        du = -(rF / th) - (zwv / (th * th))
+    else:
+        du = -(rF / th)
+    return torch.where(free, du, torch.zeros_like(du))
+
+
+def _search(st: _Run, dirn: torch.Tensor, a1: float, c1: float, c2: float, maxls: int):
+    """Strong-Wolfe step on (0, 1] along ``dirn`` (the iterate stays feasible), or None.  The
+    directional derivatives are summed over the ranks with the (global) loss: one copy per
+    trial point, and the first one also carries the slope at the start point (``st.d0``)."""
+    g = st.g
+
+    def sums(ga, first):
+        parts = [(ga.double() * dirn.double()).sum()]
+        if first:
+            parts.append((g.double() * dirn.double()).sum())
+        return parts
+
+    def start_slope():
+        st.d0 = float(st.trial.last[1])
+        return st.d0
+
+    st.trial.start(st.x, dirn, sums)
+    return strong_wolfe(st.trial, st.f, start_slope, a1, c1, c2, maxls, amax=1.0)
+
+
+def _truncated(st: _Run, xcp: torch.Tensor, du: torch.Tensor) -> torch.Tensor:
+    """The direction to the feasible truncation of the subspace step (for when the
+    projected step is not a descent direction)."""
+    ratio = torch.where(du > 0, (st.hi - xcp) / du, torch.where(du < 0, (st.lo - xcp) / du,
+                                                               torch.full_like(du, math.inf)))
+    rmin_l = -ratio.min().double() if ratio.numel() else \
+        torch.full((), -math.inf, dtype=torch.float64, device=du.device)
+    rmin = -float(st.red.reduce(maxes=[rmin_l])[0])
+    return xcp + min(1.0, rmin) * du - st.x
+
+
+def _update(st: _Run, dirn: torch.Tensor, best: float) -> None:
+    """Move to the accepted trial point; the new pair goes into the spare slot and waits
+    there for copy A of the next iteration."""
+    ring = st.ring
+    f_new, g_new, _ = st.trial.cache[best]
+    q = ring.spare()
+    torch.mul(dirn, best, out=ring.s(q))
+    torch.sub(g_new, st.g, out=ring.y(q))
+    st.x.add_(ring.s(q))
+    st.x.copy_(_clip(st.x, st.lo, st.hi))
+    st.pending = q
+    st.f, st.g = f_new, g_new
+
+
+@driver(single_thread_blas=True)
+def lbfgsb_minimize(obj, lo=None, hi=None, maxiter: int = 100, m: int = 10,
                     factr: float = 1e7, pgtol: float = 1e-5, maxls: int = 20,
                     c1: float = 1e-4, c2: float = 0.9, K: Optional[int] = None,
                     callback=None, gtol: Optional[float] = None,
@@ -176,28 +285,13 @@ def _lbfgsb_minimize_impl(obj, lo=None, hi=None, maxiter: int = 100, m: int = 10
         pgtol = gtol
     if ftol is not None:
         factr = ftol / _EPS
+    ftol = factr * _EPS
     if hess_inv:
         from .invhess import check_hess_inv_objective
         check_hess_inv_objective(obj)
-    comm, sharded = obj.comm, obj.sharded
-    n = obj.n_local
-    dev = obj.device
-    lo, hi = _box(lo, hi, n, dev)
-    lo64, hi64 = lo.double(), hi.double()
-    x = torch.minimum(torch.maximum(obj.x0().contiguous(), lo), hi)
-    f, g = obj(x)
-    g = g.clone()
-    nfev = 1
-    H = _History(m, n, dev)
-    R = H.R
-    dot = MultiDot(2 * R, n, dev)
-    dev_call = getattr(obj, "device_call", None) if dev.type == "cuda" else None
-    ftol = factr * _EPS
-    pending = None  # slot of a measured, not yet accepted pair
-    status, message, nit = 1, "STOP: TOTAL NO. of ITERATIONS REACHED LIMIT", 0
-    xt = torch.empty_like(x)
-
-    red = DeviceReducer(comm, sharded, dev)  # collective (may connect peer memory)
+    red = DeviceReducer(obj.comm, obj.sharded, obj.device)  # collective (may connect peer memory)
+    st = _Run(obj, red, lo, hi, m, K)
+    ring = st.ring
     # the first Cauchy-point batch all-gathers (1 + B0) x (2 + 2m) fp64 records per rank:
     # connect that context now; the geometric growth to larger batches (rare: the Cauchy
     # point usually lies among the first few thousand breakpoints) connects its larger
@@ -205,180 +299,48 @@ def _lbfgsb_minimize_impl(obj, lo=None, hi=None, maxiter: int = 100, m: int = 10
     # 1.2 MB per rank at m = 10 instead of 11.5 MB reserved for a 2^16 batch up front
     b0 = int(K) if K is not None else min(1 << 14, _B_CAP_MULTI)
     red.reserve_gather((1 + b0) * (2 + 2 * m) * 8)
-
-    from ..utils.hooks import StepHooks
-    hooks = StepHooks(comm, what="L-BFGS-B iterate")  # MULTIGRAD_CHECK_EVERY / _METRICS
-    host0 = getattr(comm, "host_collectives", 0) if comm is not None else 0
-
-    def run_callback(xv):
-        nonlocal host0
-        h0 = getattr(comm, "host_collectives", 0) if comm is not None else 0
-        callback(obj.full(xv))
-        if comm is not None:  # the callback's own collectives are not the loop's
-            host0 += getattr(comm, "host_collectives", 0) - h0
-
+    host = HostCollectives(obj.comm)
     for k in range(maxiter + 1):
-        # ------------------------------------------------ copy A: pair dots + GCP inputs
-        t = torch.where(g < 0, (x - hi) / g, torch.where(g > 0, (x - lo) / g,
-                                                          torch.full_like(g, math.inf)))
-        t = torch.where(torch.isnan(t), torch.full_like(t, math.inf), t)
-        free_path = t > 0
-        d = torch.where(free_path, -g, torch.zeros_like(g))
-        xd = x.double()
-        pg = (torch.minimum(torch.maximum(xd - g.double(), lo64), hi64) - xd).abs()
-        vecs = [d] if pending is None else [H.s(pending), H.y(pending), d]
-        dots_dev = dot(H.HS, 2 * R, vecs)
-        tc = torch.where(free_path & torch.isfinite(t), t, torch.full_like(t, math.inf))
-        pg_l = pg.max().double() if n else torch.zeros((), dtype=torch.float64, device=dev)
-        # one reduction and one copy: [d.d, HS.vecs (summed), max|pg| (max), #finite (local)]
-        packA = red.reduce(sums=[(d.double() * d.double()).sum(), dots_dev],
-                           maxes=[pg_l], local=[torch.isfinite(tc).sum()])
-        dd = packA[0]
-        dots_np = packA[1:1 + 2 * R * len(vecs)].reshape(2 * R, len(vecs))
-        pgmax = float(packA[-2])
-        nfin_l = packA[-1]
-        if pending is not None:
-            H.accept(pending, dots_np[:, :2])
-            pending = None
-        Wd = dots_np[:, -1]  # HS rows . d
+        dd, Wd, pgmax, tc, nfin = _measure(st)
         if k > 0 and callback is not None:
-            run_callback(x)
+            host.callback(callback, obj, st.x)
         if pgmax <= pgtol:
-            status, message = 0, "CONVERGENCE: NORM_OF_PROJECTED_GRADIENT_<=_PGTOL"
+            st.converged_gradient()
             break
         if k == maxiter:
             break
-        # ------------------------------------------------ generalized Cauchy point
-        idx, M, WWt = H.compact()
-        rows, fac = H.rows(idx)
-        th = H.theta
-        tstar, cvec = _cauchy_point(dd, Wd[rows] * fac, M, th, tc, int(nfin_l), g, H.HS,
-                                    rows, fac, red, K)
-        xcp = torch.minimum(torch.maximum(x - tstar * g, lo), hi)
-        free = (xcp > lo) & (xcp < hi)
-        # ------------------------------------------------ copy B: subspace inner products
-        kk2 = idx.size
-        if kk2:
-            Mc = M @ cvec
-            coef = np.zeros(2 * R)
-            coef[rows] = Mc * fac
-            wmc = torch.empty_like(x)
-            lincomb_(H.HS, 2 * R, torch.from_numpy(coef.astype(np.float32)).to(dev), 0.0, None, wmc)
-            r = g + th * (xcp - x) - wmc
-        else:
-            r = g + th * (xcp - x)
-        rF = torch.where(free, r, torch.zeros_like(r))
-        WtZr = dot(H.HS, 2 * R, [rF])[:, 0]
-        if kk2:
-            act = torch.nonzero(~free).reshape(-1)  # a host sync: only where it is used
-            rows_d = torch.as_tensor(rows, device=dev)
-            GA = _gram(H.HS[rows_d[:, None], act[None, :]].double())
-        else:
-            GA = torch.zeros((0, 0), dtype=torch.float64, device=dev)
-        redB = red.reduce(sums=[WtZr, GA])
-        WtZr_np = redB[:2 * R]
-        GA_np = redB[2 * R:].reshape(kk2 * 2, kk2 * 2) if kk2 else np.zeros((0, 0))
-        if kk2:
-            fw = fac[:, None] * fac[None, :]
-            GF = WWt - GA_np * fw               # Gram of W over the free rows
-            v = M @ (WtZr_np[rows] * fac)
-            N = np.eye(2 * kk2) - (M @ GF) / th
-            v = scipy.linalg.solve(N, v)
-            coef = np.zeros(2 * R)
-            coef[rows] = v * fac
-            zwv = torch.empty_like(x)
-            lincomb_(H.HS, 2 * R, torch.from_numpy(coef.astype(np.float32)).to(dev), 0.0, None, zwv)
-            du = -(rF / th) - (zwv / (th * th))
-        else:
-            du = -(rF / th)
-        du = torch.where(free, du, torch.zeros_like(du))
-        xbar = torch.minimum(torch.maximum(xcp + du, lo), hi)
-        dirn = xbar - x
-        # ------------------------------------------------ line search along x + a dirn
+        mdl = _generalized_cauchy(st, dd, Wd, tc, nfin)
+        du = _subspace_step(st, mdl)
+        dirn = _clip(mdl.xcp + du, st.lo, st.hi) - st.x
         a1 = 1.0
-        if k == 0 or not H.order:
+        if k == 0 or not ring.order:
             dnorm2 = float(red.reduce(sums=[(dirn.double() ** 2).sum()])[0])
             a1 = min(1.0, 1.0 / math.sqrt(max(dnorm2, 1e-300)))
-        cache = {}
-        d0_box = [None]
-
-        def phi(alpha):
-            nonlocal nfev
-            torch.add(x, dirn, alpha=float(alpha), out=xt)
-            if dev_call is not None:
-                lt, ga = dev_call(xt)
-                ga = ga.clone()
-            else:
-                fl, ga = obj(xt)
-                ga = ga.clone()
-                lt = torch.tensor([fl], dtype=torch.float64)
-            # directional derivative(s) summed over the ranks with the (global) loss: one copy
-            parts = [(ga.double() * dirn.double()).sum()]
-            if d0_box[0] is None:
-                parts.append((g.double() * dirn.double()).sum())
-            red2 = red.reduce(sums=parts, local=[lt.reshape(1)])
-            fa = float(red2[-1])
-            if d0_box[0] is None:
-                d0_box[0] = float(red2[1])
-            nfev += 1
-            cache[alpha] = (fa, ga, float(red2[0]))
-            return fa, float(red2[0])
-
-        best = _line_search(phi, f, d0_box, a1, c1, c2, maxls)
-        if d0_box[0] is not None and d0_box[0] >= 0:
+        best = _search(st, dirn, a1, c1, c2, maxls)
+        if st.d0 >= 0:
             # the projected subspace step is not a descent direction: truncate instead
-            ratio = torch.where(du > 0, (hi - xcp) / du, torch.where(du < 0, (lo - xcp) / du,
-                                                                    torch.full_like(du, math.inf)))
-            rmin_l = -ratio.min().double() if ratio.numel() else \
-                torch.full((), -math.inf, dtype=torch.float64, device=dev)
-            rmin = -float(red.reduce(maxes=[rmin_l])[0])
-            dirn = xcp + min(1.0, rmin) * du - x
-            cache.clear()
-            d0_box[0] = None
-            best = _line_search(phi, f, d0_box, a1, c1, c2, maxls)
-        if best is None or best not in cache:
-            cands = [(v[0], a) for a, v in cache.items() if v[0] < f]
-            if not cands:
-                status, message = 2, "ABNORMAL_TERMINATION_IN_LNSRCH"
-                break
-            best = min(cands)[1]
-        f_new, g_new, _ = cache[best]
-        q = H.spare()
-        torch.mul(dirn, best, out=H.HS[q])
-        torch.sub(g_new, g, out=H.HS[R + q])
-        x.add_(H.HS[q])
-        x.copy_(torch.minimum(torch.maximum(x, lo), hi))
-        pending = q
-        nit = k + 1
-        f_old, f, g = f, f_new, g_new
-        if hooks.active:
-            hooks(k, f, None, (lambda: x) if not sharded else None, nfev=nfev)
-        if (f_old - f) <= ftol * max(abs(f_old), abs(f), 1.0):
-            status, message = 0, "CONVERGENCE: REL_REDUCTION_OF_F_<=_FACTR*EPSMCH"
-            if callback is not None:
-                run_callback(x)
+            dirn = _truncated(st, mdl.xcp, du)
+            best = _search(st, dirn, a1, c1, c2, maxls)
+        best = best_decrease(best, st.trial.cache, st.f)
+        if best is None:
+            st.no_step()
             break
-    host_calls = (getattr(comm, "host_collectives", 0) - host0) if comm is not None else 0
-    if hess_inv and pending is not None:
+        f_old = st.f
+        _update(st, dirn, best)
+        st.nit = k + 1
+        if st.hooks.active:
+            st.hooks(k, st.f, None, (lambda: st.x) if not obj.sharded else None,
+                     nfev=st.trial.nfev)
+        if st.converged_decrease(f_old, ftol):
+            if callback is not None:
+                host.callback(callback, obj, st.x)
+            break
+    host_calls = host.count
+    if hess_inv and st.pending is not None:
         # the last pair is measured at the top of the next iteration, which never came
-        pk = red.reduce(sums=[dot(H.HS, 2 * R, [H.s(pending), H.y(pending)])])
-        H.accept(pending, pk.reshape(2 * R, 2))
-        pending = None
-    red.check("L-BFGS-B")
-    if getattr(obj, "check", None) is not None:
-        obj.check("L-BFGS-B")  # the objective's own exchanges (engine: ZeRO two-shot, one-shot)
-    xf = obj.full(x)
-    if getattr(obj, "finalize", None) is not None:
-        xf = obj.finalize(x)
-    res = scipy.optimize.OptimizeResult(
-        x=xf, fun=f, jac=g, nit=nit, nfev=nfev, njev=nfev, status=status,
-        success=status == 0, message=message, host_collectives=host_calls,
-        reduction=red.describe())
-    if hess_inv:
-        from .invhess import build_hess_inv
-        res["hess_inv"] = build_hess_inv(obj, H.HS, R, H.order, H.SY, H.YY, red, x, SS=H.SS,
-                                         dot=dot)
-    return res
+        pk = red.reduce(sums=[st.dot(ring.HS, 2 * ring.R, [ring.s(st.pending), ring.y(st.pending)])])
+        st.accept_pending(pk.reshape(2 * ring.R, 2))
+    return st.result(host_calls, hess_inv, st.dot)
 
 
 def _cauchy_point(dd, p0, M, theta, tc, nfin, g, HS, rows, fac, red, K):
@@ -527,31 +489,6 @@ def _scan_batch(st, t, g, W, M, theta):
     return False, None, None
 
 
-def _line_search(phi, f0, d0_box, a1, c1, c2, maxls):
-    """Strong-Wolfe search on (0, 1] (bracketing + zoom); ``d0_box[0]`` is filled by the
-    first evaluation (the directional derivative at 0 travels with it)."""
-    alpha = a1
-    fa, da = phi(alpha)
-    d0 = d0_box[0]
-    if d0 >= 0:
-        return None
-    a_prev, f_prev, dphi_prev = 0.0, f0, d0
-    for i in range(maxls):
-        if i > 0:
-            fa, da = phi(alpha)
-        if not np.isfinite(fa) or fa > f0 + c1 * alpha * d0 or (i > 0 and fa >= f_prev):
-            return _zoom(phi, a_prev, alpha, f_prev, fa, dphi_prev, da, f0, d0, c1, c2, maxls)
-        if abs(da) <= -c2 * d0:
-            return alpha
-        if da >= 0 or alpha >= 1.0:
-            if da >= 0:
-                return _zoom(phi, alpha, a_prev, fa, f_prev, da, dphi_prev, f0, d0, c1, c2, maxls)
-            return alpha  # the step to the projected point: accept (sufficient decrease holds)
-        a_prev, f_prev, dphi_prev = alpha, fa, da
-        alpha = min(1.0, alpha * 2.0)
-    return None
-
-
 def run_lbfgsb_device(loss_and_grad_fn, params, maxsteps: int = 100, param_bounds=None,
                       randkey=None, comm=None, history: int = 10, **kw):
     """Device L-BFGS-B for a generic ``loss_and_grad_fn(params[, randkey])`` (replicated).
@@ -587,16 +524,3 @@ def bounds_arrays(param_bounds, n: int):
         if c is not None:
             hi[i] = float(c)
     return lo.astype(np.float32), hi.astype(np.float32)
-
-
-def lbfgsb_minimize(*args, **kwargs):
-    """See ``_lbfgsb_minimize_impl``; runs with the BLAS pools limited to one thread (the host-side
-    compact-form solves are tiny; a spinning BLAS pool would slow the CPU evaluations)."""
-    from ..utils.hooks import driver_guard
-    from ..utils.tensors import blas_single_thread
-    obj = args[0] if args else kwargs.get("obj")
-    with driver_guard(getattr(obj, "comm", None)), blas_single_thread():
-        return _lbfgsb_minimize_impl(*args, **kwargs)
-
-
-lbfgsb_minimize.__doc__ = _lbfgsb_minimize_impl.__doc__
