@@ -126,6 +126,12 @@ void compact_diag(torch::Tensor H, torch::Tensor rows, torch::Tensor fac, torch:
                   double h0, c10::optional<torch::Tensor> scale, int64_t n, torch::Tensor out);
 // gram.hip
 torch::Tensor weighted_gram(torch::Tensor J, c10::optional<torch::Tensor> w, int64_t nrows);
+// box_dual.hip
+torch::Tensor box_dual_pass(torch::Tensor J, torch::Tensor coef, torch::Tensor d, double lam,
+                            torch::Tensor lo, torch::Tensor hi,
+                            c10::optional<torch::Tensor> delta_out);
+bool box_dual_vector_loads(torch::Tensor J, torch::Tensor d, torch::Tensor lo, torch::Tensor hi,
+                           c10::optional<torch::Tensor> delta_out);
 // smf_jacobian.hip
 void smf_jacobian_lanes(torch::Tensor slot_pop, torch::Tensor slot_part, torch::Tensor theta,
                         torch::Tensor resid, int64_t s0, int64_t s1, std::vector<double> scale,
@@ -293,6 +299,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("lincomb_cols", &mg::lincomb_cols);
   m.def("compact_diag", &mg::compact_diag);
   m.def("weighted_gram", &mg::weighted_gram);
+  m.def("box_dual_pass", &mg::box_dual_pass);
+  m.def("box_dual_vector_loads", &mg::box_dual_vector_loads);
   m.def("smf_jacobian_lanes", &mg::smf_jacobian_lanes);
   m.def("hmc_workspace", &mg::hmc_workspace);
   m.def("hmc_leapfrog", &mg::hmc_leapfrog);

@@ -754,7 +754,7 @@ class OnePointModel(_OptimizerFrontEnds):
         (:func:`multigrad_amd.optim.gauss_newton.run_gauss_newton`).  Each iteration takes one
         sumstat Jacobian (``mode`` as in :meth:`calc_sumstats_jacobian_from_params`) and one
         loss evaluation per trial step; ``randkey`` is held constant.  Parameter bounds are
-        not offered.
+        not offered here: :meth:`run_gauss_newton_box` takes them.
 
         ``solver="dense"`` forms the ``[ndim, ndim]`` Gauss-Newton matrix and solves on the
         host (thousands of parameters at most).  ``solver="dual"`` solves the same damped
@@ -767,8 +767,8 @@ class OnePointModel(_OptimizerFrontEnds):
         ``ndim > 8192``, where the dense float64 matrix passes 0.5 GB."""
         from ..optim import gauss_newton as _gn
         if param_bounds is not None:
-            raise ValueError("run_gauss_newton does not offer parameter bounds; use run_bfgs "
-                             "or run_adam for a bounded fit")
+            raise ValueError("run_gauss_newton does not offer parameter bounds; use "
+                             "run_gauss_newton_box (or run_bfgs, run_adam) for a bounded fit")
         if solver not in ("auto", "dense", "dual"):
             raise ValueError(f"solver must be 'auto', 'dense' or 'dual', got {solver!r}")
         key = None if randkey is None else (
@@ -783,6 +783,30 @@ class OnePointModel(_OptimizerFrontEnds):
             lambda x: self._gauss_newton(x, key, mode, True),
             lambda x: self.calc_loss_from_params(x, randkey=key),
             x0, maxsteps=maxsteps, damping=damping, ftol=ftol, gtol=gtol, comm=self.comm)
+
+    def run_gauss_newton_box(self, guess, param_bounds=None, max_step=None, maxsteps: int = 50,
+                             randkey=None, damping: float = 1e-3, min_damping: float = 1e-4,
+                             ftol: float = 2.2e-9, gtol: float = 1e-8, inner_passes: int = 40,
+                             mode: str = "auto"):
+        """Damped Gauss-Newton fit from ``guess`` inside ``param_bounds`` (a reference-style
+        ``(ndim, 2)`` spec, ``None`` for an open side) and with no parameter moving by more
+        than ``max_step`` (a scalar or ``[ndim]``, in parameter units) in one step
+        (:func:`multigrad_amd.optim.gauss_newton_box.run_gauss_newton_box`).  Every trial step
+        is the exact minimiser of the damped model inside that box, found through its
+        ``K x K`` dual, so every point the loss sees lies inside the bounds.  It always runs
+        the dual form: ``res.x``, ``res.jac`` and ``res.active`` are tensors on the
+        parameters' device, ``res.hess_inv`` is an operator and ``res.solver == "dual-box"``.
+        ``mode`` and ``randkey`` as in :meth:`run_gauss_newton`."""
+        from ..optim import gauss_newton_box as _gnb
+        key = None if randkey is None else (
+            randkey if hasattr(randkey, "split") else init_randkey(randkey))
+        x0 = as_param_tensor(guess, device=self.param_device(), dtype=self.dtype)
+        return _gnb.run_gauss_newton_box(
+            lambda x: self._gauss_newton_factors(x, key, mode, True),
+            lambda x: self.calc_loss_from_params(x, randkey=key),
+            x0, param_bounds=param_bounds, max_step=max_step, maxsteps=maxsteps,
+            damping=damping, min_damping=min_damping, ftol=ftol, gtol=gtol,
+            inner_passes=inner_passes, comm=self.comm)
 
     # ------------------------------------------------------------------ identity
     def __hash__(self):

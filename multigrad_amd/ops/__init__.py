@@ -4,7 +4,7 @@ from ._ext import available, ext
 __all__ = ["available", "ext", "gaussian_binned_sum", "gaussian_binned_sum_2d",
            "gaussian_binned_sum_multi", "gaussian_binned_sum_by_group",
            "gaussian_binned_sum_fine", "FineBins", "GroupIndex", "group_gather", "segment_sum",
-           "weighted_gram"]
+           "weighted_gram", "box_dual_pass"]
 
 
 def __getattr__(name):  # lazy: importing the package loads no op module and no device
@@ -29,4 +29,7 @@ def __getattr__(name):  # lazy: importing the package loads no op module and no 
     if name == "weighted_gram":
         from .gram import weighted_gram
         return weighted_gram
+    if name == "box_dual_pass":
+        from .box_dual import box_dual_pass
+        return box_dual_pass
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
