@@ -17,6 +17,7 @@
 // the bounded p output, +4 B for the trajectory) -> HBM-bandwidth bound; float4 lanes.
 #include "adam.h"
 #include "common.h"
+#include "sweep_host.h"
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -121,8 +122,6 @@ __global__ __launch_bounds__(kAdamThreads) void fused_adam_kernel(AdamArgs a) {
     }
   }
 }
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 void fused_adam(torch::Tensor u, torch::Tensor m, torch::Tensor v, torch::Tensor g,
                 c10::optional<torch::Tensor> p, c10::optional<torch::Tensor> lo,

@@ -11,6 +11,7 @@
 
 #include "binned_common.h"
 #include "smf_host.h"
+#include "sweep_host.h"
 
 namespace mg {
 
@@ -29,8 +30,6 @@ inline int padded_bins(int nb, const char* op_name, const char* axis = "") {
     default: { constexpr int NAME = 32; __VA_ARGS__; break; } \
   }
 #define MG_DISPATCH_BINNED(NBP, ...) MG_DISPATCH_PAD(NBP, NB, __VA_ARGS__)
-
-inline bool aligned16(const void* p) { return aligned_to(p, 16); }
 
 // Workgroups that fill the chip once (occupancy x CU count of the device), per kernel.
 template <auto Kernel>

@@ -22,14 +22,16 @@
 // shuffles, LDS, one slab row per workgroup, and a final per-entry reduce kernel that also
 // mirrors the lower triangle of W.  No atomics: bitwise reproducible for a fixed n and
 // device.  The reciprocal 1 / (lam d) is taken once per column and serves sigma and W.
+// The group loads, the slab-row store, the slab entry sum and the triangle decode are
+// sweep_device.h's; the cap, the grid and the row-tile dispatch are sweep_host.h's.
 //
 // Loads are 16 bytes wide when every pointer, the row stride and n allow it (the last n % 4
 // columns by guarded scalar loads); otherwise every load is a guarded scalar load.
-#include "common.h"
+#include "sweep_device.h"
+#include "sweep_host.h"
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include <algorithm>
 
 namespace mg {
 
@@ -85,6 +87,27 @@ __device__ __forceinline__ void box_dual_accumulate(const float (&x)[T][G], cons
   }
 }
 
+// Column group j of the sweep: loads, sums and the delta store.
+template <int T, int G>
+__device__ __forceinline__ void box_dual_group(int64_t j, const float* (&row)[T],
+                                               const double (&a)[T], const float* d,
+                                               const float* lo, const float* hi, double lam,
+                                               float* delta_out,
+                                               double (&acc)[BoxAcc<T>::kEntries]) {
+  float x[T][G], dv[G], lov[G], hiv[G], dout[G];
+  load_group<G>(d, j, dv);
+  load_group<G>(lo, j, lov);
+  load_group<G>(hi, j, hiv);
+  load_group_rows<T, G>(row, j, x);
+  box_dual_accumulate<T, G>(x, a, dv, lov, hiv, lam, acc, dout);
+  if (delta_out) {
+    if constexpr (G == 4)
+      reinterpret_cast<float4*>(delta_out)[j] = make_float4(dout[0], dout[1], dout[2], dout[3]);
+    else
+      delta_out[j] = dout[0];
+  }
+}
+
 // grid.x: column slices (grid-stride).  Row indices past K are clamped to the last row with
 // a zero coefficient (their sums are never read).
 template <int T, bool VEC>
@@ -106,60 +129,19 @@ __global__ __launch_bounds__(kBoxThreads) void box_dual_kernel(
   for (int e = 0; e < NE; ++e) acc[e] = 0.0;
   const int64_t tid = (int64_t)blockIdx.x * kBoxThreads + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * kBoxThreads;
+  // float4 groups first, then single columns; the loops stay here: inside a helper they
+  // cost box_dual_kernel<1, true> 20 VGPRs
   int64_t j0 = 0;
   if constexpr (VEC) {
     const int64_t n4 = n >> 2;
-    for (int64_t j = tid; j < n4; j += stride) {
-      float x[T][4], dv[4], lov[4], hiv[4], dout[4];
-      {
-        const float4 v = reinterpret_cast<const float4*>(d)[j];
-        dv[0] = v.x; dv[1] = v.y; dv[2] = v.z; dv[3] = v.w;
-      }
-      {
-        const float4 v = reinterpret_cast<const float4*>(lo)[j];
-        lov[0] = v.x; lov[1] = v.y; lov[2] = v.z; lov[3] = v.w;
-      }
-      {
-        const float4 v = reinterpret_cast<const float4*>(hi)[j];
-        hiv[0] = v.x; hiv[1] = v.y; hiv[2] = v.z; hiv[3] = v.w;
-      }
-#pragma unroll
-      for (int k = 0; k < T; ++k) {
-        const float4 v = reinterpret_cast<const float4*>(row[k])[j];
-        x[k][0] = v.x; x[k][1] = v.y; x[k][2] = v.z; x[k][3] = v.w;
-      }
-      box_dual_accumulate<T, 4>(x, a, dv, lov, hiv, lam, acc, dout);
-      if (delta_out)
-        reinterpret_cast<float4*>(delta_out)[j] = make_float4(dout[0], dout[1], dout[2], dout[3]);
-    }
+    for (int64_t j = tid; j < n4; j += stride)
+      box_dual_group<T, 4>(j, row, a, d, lo, hi, lam, delta_out, acc);
     j0 = n4 << 2;
   }
-  for (int64_t j = j0 + tid; j < n; j += stride) {
-    float x[T][1], dv[1], lov[1], hiv[1], dout[1];
-    dv[0] = d[j];
-    lov[0] = lo[j];
-    hiv[0] = hi[j];
-#pragma unroll
-    for (int k = 0; k < T; ++k) x[k][0] = row[k][j];
-    box_dual_accumulate<T, 1>(x, a, dv, lov, hiv, lam, acc, dout);
-    if (delta_out) delta_out[j] = dout[0];
-  }
-  // fixed-order block sums, 8 entries at a time, into this workgroup's slab row
+  for (int64_t j = j0 + tid; j < n; j += stride)
+    box_dual_group<T, 1>(j, row, a, d, lo, hi, lam, delta_out, acc);
   double* out = slab + (int64_t)blockIdx.x * NE;
-  __shared__ double scratch[8 * (kBoxThreads / kWave)];
-#pragma unroll
-  for (int e0 = 0; e0 < NE; e0 += 8) {
-    double v[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v[q] = e0 + q < NE ? acc[e0 + q] : 0.0;
-    block_sum_n<8>(v, scratch);
-    if (threadIdx.x == 0) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q)
-        if (e0 + q < NE) out[e0 + q] = v[q];
-    }
-    __syncthreads();
-  }
+  slab_row_store<kBoxThreads>(out, acc);
 }
 
 // One workgroup per slab entry e: the fixed-order sum over the bx slab rows, written to its
@@ -172,12 +154,8 @@ __global__ __launch_bounds__(kBoxThreads) void box_dual_reduce_kernel(
   if (e < T) {
     if (e < K) at = e;
   } else if (e < T + tri) {
-    int rem = e - T, k = 0;
-    while (rem >= T - k) {
-      rem -= T - k;
-      ++k;
-    }
-    const int l = k + rem;
+    int k, l;
+    triangle_index(e - T, T, k, l);
     if (l < K) {
       at = K + (int64_t)k * K + l;
       mirror = K + (int64_t)l * K + k;
@@ -186,13 +164,11 @@ __global__ __launch_bounds__(kBoxThreads) void box_dual_reduce_kernel(
     at = K + (int64_t)K * K + (e - T - tri);
   }
   if (at < 0) return;
-  double s[1] = {0.0};
-  for (int r = threadIdx.x; r < bx; r += kBoxThreads) s[0] += slab[(int64_t)r * ne + e];
-  __shared__ double scratch[kBoxThreads / kWave];
-  block_sum_n<1>(s, scratch);
+  const double s =
+      slab_entry_sum<kBoxThreads>(bx, [&](int r) { return slab[(int64_t)r * ne + e]; });
   if (threadIdx.x == 0) {
-    out[at] = s[0];
-    if (mirror >= 0) out[mirror] = s[0];
+    out[at] = s;
+    if (mirror >= 0) out[mirror] = s;
   }
 }
 
@@ -204,25 +180,13 @@ static void launch_box_dual(const float* J, int64_t ld, int K, const double* coe
   constexpr int NE = BoxAcc<T>::kEntries;
   auto kv = box_dual_kernel<T, true>;
   auto ks = box_dual_kernel<T, false>;
-  static int cap = 0;  // resident workgroups of this instantiation
-  if (cap == 0) {
-    int dev = 0, cus = 0, per = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kv, kBoxThreads, 0);
-    cap = std::max(1, std::min(kBoxMaxBlocks, std::max(1, cus) * std::max(1, per)));
-  }
-  const int64_t chunks = vec ? (n >> 2) + (n & 3) : n;
-  const int64_t bx =
-      std::max<int64_t>(1, std::min<int64_t>((chunks + kBoxThreads - 1) / kBoxThreads, cap));
+  static GridCap cap;  // of the 16-byte-load instantiation: one grid for both load paths
+  const int64_t bx = chunk_grid(sweep_chunks(n, vec), kBoxThreads,
+                                resident_cap(cap, kBoxMaxBlocks, kBoxThreads, kv));
   auto slab = torch::empty({bx * NE}, like.options().dtype(at::kDouble));
   double* sp = slab.data_ptr<double>();
-  if (vec)
-    hipLaunchKernelGGL(kv, dim3((unsigned)bx), dim3(kBoxThreads), 0, stream, J, ld, K, coef, d, lam,
-                       lo, hi, n, delta_out, sp);
-  else
-    hipLaunchKernelGGL(ks, dim3((unsigned)bx), dim3(kBoxThreads), 0, stream, J, ld, K, coef, d, lam,
-                       lo, hi, n, delta_out, sp);
+  hipLaunchKernelGGL(vec ? kv : ks, dim3((unsigned)bx), dim3(kBoxThreads), 0, stream, J, ld, K,
+                     coef, d, lam, lo, hi, n, delta_out, sp);
   hipLaunchKernelGGL(box_dual_reduce_kernel, dim3(NE), dim3(kBoxThreads), 0, stream, sp, (int)bx,
                      NE, T, K, out);
 }
@@ -231,9 +195,8 @@ static void launch_box_dual(const float* J, int64_t ld, int K, const double* coe
 // multiple of 4 floats apart and at least one float4 of columns.
 static bool box_vector_loads(const float* J, int K, int64_t ld, const float* d, const float* lo,
                              const float* hi, const float* delta_out, int64_t n) {
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  return al16(J) && (K == 1 || ld % 4 == 0) && al16(d) && al16(lo) && al16(hi) &&
-         (!delta_out || al16(delta_out)) && n >= 4;
+  return aligned16(J) && (K == 1 || ld % 4 == 0) && aligned16(d) && aligned16(lo) &&
+         aligned16(hi) && (!delta_out || aligned16(delta_out)) && n >= 4;
 }
 
 // The same decision for the tensors of a call (tests and benchmarks record the path with it).
@@ -286,13 +249,9 @@ torch::Tensor box_dual_pass(torch::Tensor J, torch::Tensor coef, torch::Tensor d
   const bool vec = box_vector_loads(jp, K, ld, dd, lp, hp, dp, n);
   const double* cp = coef.data_ptr<double>();
   double* op = out.data_ptr<double>();
-#define MG_BOX(T) launch_box_dual<T>(jp, ld, K, cp, dd, lam, lp, hp, n, vec, dp, op, J, stream)
-  if (K <= 1) MG_BOX(1);
-  else if (K <= 2) MG_BOX(2);
-  else if (K <= 4) MG_BOX(4);
-  else if (K <= 8) MG_BOX(8);
-  else MG_BOX(10);
-#undef MG_BOX
+  dispatch_row_tile<kBoxMaxRows>(K, [&](auto tile) {
+    launch_box_dual<decltype(tile)::value>(jp, ld, K, cp, dd, lam, lp, hp, n, vec, dp, op, J, stream);
+  });
   return out;
 }
 

@@ -10,18 +10,20 @@
 // and the third factor enters by one fused multiply-add), and the per-thread sums are
 // reduced in a fixed order: wave shuffles, LDS, one slab row per workgroup, and a final
 // per-entry reduce kernel that also mirrors the lower triangle.  No atomics: the result is
-// bitwise reproducible for a fixed n and device.
+// bitwise reproducible for a fixed n and device.  The reduce kernel's sum and the triangle
+// decode are sweep_device.h's, the cap, the grid and the row-tile dispatch sweep_host.h's; the
+// main kernel's loads and slab-row store are written out here (see the note in the kernel).
 //
 // K > 16 is tiled over pairs of 8-row blocks (grid.y, block pairs bi <= bj with a full
 // 8 x 8 tile each), so J is re-read once per row block: (K / 8 + 1) / 2 passes per row.
 //
 // Loads are 16 bytes wide when the pointers, the row stride and n allow it (the last
 // n % 4 columns by guarded scalar loads); otherwise every load is a guarded scalar load.
-#include "common.h"
+#include "sweep_device.h"
+#include "sweep_host.h"
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include <algorithm>
 
 namespace mg {
 
@@ -70,14 +72,7 @@ __global__ __launch_bounds__(kGramThreads) void weighted_gram_kernel(
     int64_t n, double* __restrict__ slab) {
   constexpr int NE = GramTile<T, FULL>::kEntries;
   int bi = 0, bj = 0;
-  if constexpr (FULL) {
-    int rem = blockIdx.y;
-    while (rem >= nrb - bi) {
-      rem -= nrb - bi;
-      ++bi;
-    }
-    bj = bi + rem;
-  }
+  if constexpr (FULL) triangle_index(blockIdx.y, nrb, bi, bj);
   const float* ri[T];
   const float* rj[T];
 #pragma unroll
@@ -90,6 +85,9 @@ __global__ __launch_bounds__(kGramThreads) void weighted_gram_kernel(
   for (int e = 0; e < NE; ++e) acc[e] = 0.0;
   const int64_t tid = (int64_t)blockIdx.x * kGramThreads + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * kGramThreads;
+  // The sweep and the slab-row store are written out (box_dual.hip uses sweep_device.h for
+  // both): at T = 16 this kernel sits at the register limit, and any other spelling of them
+  // changes its allocation.
   int64_t j0 = 0;
   if constexpr (VEC) {
     const int64_t n4 = n >> 2;
@@ -130,7 +128,6 @@ __global__ __launch_bounds__(kGramThreads) void weighted_gram_kernel(
       gram_accumulate<T, FULL, 1>(xi, xi, wv, acc);
     }
   }
-  // fixed-order block sums, 8 entries at a time, into this workgroup's slab row
   double* out = slab + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * NE;
   __shared__ double scratch[8 * (kGramThreads / kWave)];
 #pragma unroll
@@ -156,32 +153,19 @@ __global__ __launch_bounds__(kGramThreads) void weighted_gram_reduce_kernel(
   const int pair = blockIdx.x / ne, e = blockIdx.x % ne;
   int bi = 0, bj = 0, a = 0, b = 0;
   if (full) {
-    int rem = pair;
-    while (rem >= nrb - bi) {
-      rem -= nrb - bi;
-      ++bi;
-    }
-    bj = bi + rem;
+    triangle_index(pair, nrb, bi, bj);
     a = e / T;
     b = e % T;
   } else {
-    int rem = e;
-    while (rem >= T - a) {
-      rem -= T - a;
-      ++a;
-    }
-    b = a + rem;
+    triangle_index(e, T, a, b);
   }
   const int k = bi * T + a, l = bj * T + b;
   if (k >= K || l >= K || k > l) return;  // uniform per workgroup
-  double s[1] = {0.0};
-  for (int r = threadIdx.x; r < bx; r += kGramThreads)
-    s[0] += slab[((int64_t)r * npairs + pair) * ne + e];
-  __shared__ double scratch[kGramThreads / kWave];
-  block_sum_n<1>(s, scratch);
+  const double s = slab_entry_sum<kGramThreads>(
+      bx, [&](int r) { return slab[((int64_t)r * npairs + pair) * ne + e]; });
   if (threadIdx.x == 0) {
-    out[(int64_t)k * K + l] = s[0];
-    out[(int64_t)l * K + k] = s[0];
+    out[(int64_t)k * K + l] = s;
+    out[(int64_t)l * K + k] = s;
   }
 }
 
@@ -191,26 +175,16 @@ static void launch_gram(const float* J, int64_t ld, int K, const float* w, int64
   constexpr int NE = GramTile<T, FULL>::kEntries;
   auto kv = weighted_gram_kernel<T, FULL, true>;
   auto ks = weighted_gram_kernel<T, FULL, false>;
-  static int cap = 0;  // resident workgroups of this instantiation
-  if (cap == 0) {
-    int dev = 0, cus = 0, per = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kv, kGramThreads, 0);
-    cap = std::max(1, std::min(kGramMaxBlocks, std::max(1, cus) * std::max(1, per)));
-  }
+  static GridCap cap;  // of the 16-byte-load instantiation: one grid for both load paths
   const int nrb = FULL ? (K + T - 1) / T : 1;
   const int npairs = nrb * (nrb + 1) / 2;
-  const int64_t chunks = vec ? (n >> 2) + (n & 3) : n;
-  int64_t bx = std::max<int64_t>(1, std::min<int64_t>((chunks + kGramThreads - 1) / kGramThreads, cap));
+  int64_t bx = chunk_grid(sweep_chunks(n, vec), kGramThreads,
+                          resident_cap(cap, kGramMaxBlocks, kGramThreads, kv));
   if (FULL) bx = std::max<int64_t>(1, std::min<int64_t>(bx, kGramTiledBlocks / npairs));
   auto slab = torch::empty({bx * npairs * NE}, like.options().dtype(at::kDouble));
   double* sp = slab.data_ptr<double>();
   dim3 grid((unsigned)bx, (unsigned)npairs);
-  if (vec)
-    hipLaunchKernelGGL(kv, grid, dim3(kGramThreads), 0, stream, J, ld, K, nrb, w, n, sp);
-  else
-    hipLaunchKernelGGL(ks, grid, dim3(kGramThreads), 0, stream, J, ld, K, nrb, w, n, sp);
+  hipLaunchKernelGGL(vec ? kv : ks, grid, dim3(kGramThreads), 0, stream, J, ld, K, nrb, w, n, sp);
   hipLaunchKernelGGL(weighted_gram_reduce_kernel, dim3(npairs * NE), dim3(kGramThreads), 0, stream,
                      sp, (int)bx, npairs, NE, T, FULL ? 1 : 0, nrb, K, out);
 }
@@ -235,16 +209,14 @@ torch::Tensor weighted_gram(torch::Tensor J, c10::optional<torch::Tensor> w, int
   auto stream = at::hip::getCurrentHIPStream();
   const float* jp = J.data_ptr<float>();
   const int64_t ld = J.size(0) > 1 ? J.stride(0) : n;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool vec = al16(jp) && (K == 1 || ld % 4 == 0) && (!wp || al16(wp)) && n >= 4;
+  const bool vec = aligned16(jp) && (K == 1 || ld % 4 == 0) && (!wp || aligned16(wp)) && n >= 4;
   double* op = out.data_ptr<double>();
-  if (K <= 1) launch_gram<1, false>(jp, ld, K, wp, n, vec, op, J, stream);
-  else if (K <= 2) launch_gram<2, false>(jp, ld, K, wp, n, vec, op, J, stream);
-  else if (K <= 4) launch_gram<4, false>(jp, ld, K, wp, n, vec, op, J, stream);
-  else if (K <= 8) launch_gram<8, false>(jp, ld, K, wp, n, vec, op, J, stream);
-  else if (K <= 10) launch_gram<10, false>(jp, ld, K, wp, n, vec, op, J, stream);
-  else if (K <= 16) launch_gram<16, false>(jp, ld, K, wp, n, vec, op, J, stream);
-  else launch_gram<kGramTile, true>(jp, ld, K, wp, n, vec, op, J, stream);
+  if (K <= 16)
+    dispatch_row_tile<16>(K, [&](auto tile) {
+      launch_gram<decltype(tile)::value, false>(jp, ld, K, wp, n, vec, op, J, stream);
+    });
+  else
+    launch_gram<kGramTile, true>(jp, ld, K, wp, n, vec, op, J, stream);
   return out;
 }
 

@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "smf_host.h"
+#include "sweep_host.h"
 
 namespace mg {
 
@@ -38,8 +39,6 @@ constexpr int kGrpWaves = kGrpThreads / kWave;
 constexpr int kKeyNone = -1;                 // an unused carry slot
 constexpr int kKeyPast = -2;                 // a position beyond the list
 constexpr int kKeyEdge = -3;                 // the neighbour of the first / last entry
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <auto Kernel>
 int64_t chip_blocks() {

@@ -17,17 +17,18 @@
 // pointers 16-byte aligned) or as guarded scalars (any other view, and the last partial
 // chunk), and the grid is the same for both, so the energies are bitwise equal on both
 // load paths and from run to run for a fixed n and device.  The elementwise updates are
-// written with explicit fmaf, the same on both paths.
+// written with explicit fmaf, the same on both paths.  The final sum is sweep_device.h's slab
+// entry sum; the cap over a kernel family and the grid are sweep_host.h's.
 //
 // gfx950 (hipcc -O3), VGPRs per instantiation <VEC, BCAST>; no scratch, 8 waves per SIMD:
 //   hmc_leapfrog_kernel  <1,0> 30  <1,1> 30  <0,0> 30  <0,1> 30
 //   hmc_momentum_kernel  <1,0> 25  <1,1> 22  <0,0> 25  <0,1> 21
 //   hmc_commit_kernel    <1> 33    <0> 30      hmc_reduce_kernel 18
-#include "common.h"
+#include "sweep_device.h"
+#include "sweep_host.h"
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include <algorithm>
 
 namespace mg {
 
@@ -141,11 +142,8 @@ __global__ __launch_bounds__(kHmcThreads) void hmc_momentum_kernel(
 // shuffle/LDS tree (one workgroup).
 __global__ __launch_bounds__(kHmcThreads) void hmc_reduce_kernel(
     const double* __restrict__ partial, int nblk, double* __restrict__ out) {
-  double s[1] = {0.0};
-  for (int b = threadIdx.x; b < nblk; b += kHmcThreads) s[0] += partial[b];
-  __shared__ double scratch[kHmcThreads / kWave];
-  block_sum_n<1>(s, scratch);
-  if (threadIdx.x == 0) out[0] = 0.5 * s[0];
+  const double s = slab_entry_sum<kHmcThreads>(nblk, [&](int b) { return partial[b]; });
+  if (threadIdx.x == 0) out[0] = 0.5 * s;
 }
 
 // Welford with the count that includes this vector (rc = 1 / count):
@@ -190,37 +188,11 @@ __global__ __launch_bounds__(kHmcThreads) void hmc_commit_kernel(
 // launch_dot / the streaming passes of lbfgs.hip).  One cap per kernel family -- the least
 // of its instantiations -- so the float4 and the scalar path launch the same grid and sum
 // their energies in the same order.
-constexpr int kHmcCapDevices = 64;
-struct HmcCap {
-  int v[kHmcCapDevices] = {};
-};
-
 template <typename... K>
-static int hmc_cap(HmcCap& cap, K... kernels) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const bool keep = dev >= 0 && dev < kHmcCapDevices;
-  if (keep && cap.v[dev] != 0) return cap.v[dev];
-  int cus = 0;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  int per = 1 << 30;
-  auto one = [&](auto k) {
-    int v = 0;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, k, kHmcThreads, 0);
-    per = std::min(per, std::max(1, v));
-  };
-  (one(kernels), ...);
-  const int c = std::max(1, std::min(kHmcMaxBlocks, std::max(1, cus) * per));
-  if (keep) cap.v[dev] = c;
-  return c;
+static int hmc_grid(int64_t n, GridCap& cap, K... kernels) {
+  return chunk_grid((n + 3) >> 2, kHmcThreads,
+                    resident_cap(cap, kHmcMaxBlocks, kHmcThreads, kernels...));
 }
-
-static int hmc_grid(int64_t n, int cap) {
-  const int64_t chunks = (n + 3) >> 2;
-  return (int)std::max<int64_t>(1, std::min<int64_t>((chunks + kHmcThreads - 1) / kHmcThreads, cap));
-}
-
-static bool hmc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 static void check_vec(const torch::Tensor& t, int64_t n, const char* what) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == n,
@@ -267,13 +239,12 @@ void hmc_leapfrog(torch::Tensor q, torch::Tensor p, torch::Tensor g, torch::Tens
   const float* gp = g.data_ptr<float>();
   const float* mp = inv_mass.data_ptr<float>();
   TORCH_CHECK(qp != pp && qp != gp && pp != gp, "q, p and g must be distinct vectors");
-  const bool vec = hmc_aligned16(qp) && hmc_aligned16(pp) && hmc_aligned16(gp) &&
-                   (bcast || hmc_aligned16(mp));
-  static HmcCap cap;
-  const int blocks = hmc_grid(n, hmc_cap(cap, hmc_leapfrog_kernel<true, false>,
-                                         hmc_leapfrog_kernel<true, true>,
-                                         hmc_leapfrog_kernel<false, false>,
-                                         hmc_leapfrog_kernel<false, true>));
+  const bool vec = aligned16(qp) && aligned16(pp) && aligned16(gp) &&
+                   (bcast || aligned16(mp));
+  static GridCap cap;
+  const int blocks = hmc_grid(n, cap, hmc_leapfrog_kernel<true, false>,
+                              hmc_leapfrog_kernel<true, true>, hmc_leapfrog_kernel<false, false>,
+                              hmc_leapfrog_kernel<false, true>);
   auto stream = at::hip::getCurrentHIPStream();
   const float af = (float)a, bf = (float)b;
   auto go = [&](auto k) {
@@ -306,12 +277,11 @@ void hmc_momentum(torch::Tensor z, torch::Tensor inv_mass, torch::Tensor p,
   float* pp = p.data_ptr<float>();
   const float* mp = inv_mass.data_ptr<float>();
   TORCH_CHECK(zp != pp, "z and p must be distinct vectors");
-  const bool vec = hmc_aligned16(zp) && hmc_aligned16(pp) && (bcast || hmc_aligned16(mp));
-  static HmcCap cap;
-  const int blocks = hmc_grid(n, hmc_cap(cap, hmc_momentum_kernel<true, false>,
-                                         hmc_momentum_kernel<true, true>,
-                                         hmc_momentum_kernel<false, false>,
-                                         hmc_momentum_kernel<false, true>));
+  const bool vec = aligned16(zp) && aligned16(pp) && (bcast || aligned16(mp));
+  static GridCap cap;
+  const int blocks = hmc_grid(n, cap, hmc_momentum_kernel<true, false>,
+                              hmc_momentum_kernel<true, true>, hmc_momentum_kernel<false, false>,
+                              hmc_momentum_kernel<false, true>);
   auto stream = at::hip::getCurrentHIPStream();
   auto go = [&](auto k) {
     hipLaunchKernelGGL(k, dim3(blocks), dim3(kHmcThreads), 0, stream, zp, mp, pp, n, partial);
@@ -334,7 +304,7 @@ void hmc_commit(torch::Tensor q, int64_t count, c10::optional<torch::Tensor> mea
   const int64_t n = q.numel();
   check_vec(q, n, "q");
   const float* qp = q.data_ptr<float>();
-  bool vec = hmc_aligned16(qp);
+  bool vec = aligned16(qp);
   float *ap = nullptr, *sp = nullptr, *tp = nullptr, *rp = nullptr;
   const int64_t* ip = nullptr;
   int64_t ntrack = 0;
@@ -345,7 +315,7 @@ void hmc_commit(torch::Tensor q, int64_t count, c10::optional<torch::Tensor> mea
     ap = mean->data_ptr<float>();
     sp = m2->data_ptr<float>();
     TORCH_CHECK(ap != sp && ap != qp && sp != qp, "q, mean and m2 must be distinct vectors");
-    vec = vec && hmc_aligned16(ap) && hmc_aligned16(sp);
+    vec = vec && aligned16(ap) && aligned16(sp);
   }
   if (has(track_idx)) {
     TORCH_CHECK(has(track_row), "track_idx needs track_row");
@@ -360,13 +330,15 @@ void hmc_commit(torch::Tensor q, int64_t count, c10::optional<torch::Tensor> mea
     check_vec(*sample_row, n, "sample_row");
     rp = sample_row->data_ptr<float>();
     TORCH_CHECK(rp != qp, "sample_row must not be q");
-    vec = vec && hmc_aligned16(rp);
+    vec = vec && aligned16(rp);
   }
   const bool pass = (ap != nullptr || rp != nullptr) && n > 0;
   if (!pass && ntrack == 0) return;
-  static HmcCap cap;
-  const int c = hmc_cap(cap, hmc_commit_kernel<true>, hmc_commit_kernel<false>);
-  const int blocks = std::max(pass ? hmc_grid(n, c) : 1, hmc_grid(4 * ntrack, c));
+  static GridCap cap;
+  auto grid = [&](int64_t len) {
+    return hmc_grid(len, cap, hmc_commit_kernel<true>, hmc_commit_kernel<false>);
+  };
+  const int blocks = std::max(pass ? grid(n) : 1, grid(4 * ntrack));
   const float rc = (float)(1.0 / (double)std::max<int64_t>(count, 1));
   auto stream = at::hip::getCurrentHIPStream();
   if (vec)

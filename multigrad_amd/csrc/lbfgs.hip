@@ -9,8 +9,10 @@
 // fp64 fixed-order block and slab reductions: deterministic), and all-reduced across
 // ranks as one device all-reduce (optim/_reduce.py: the wide one-shot peer-memory kernel,
 // else RCCL).  The search direction d = -(gamma g + sum_i c_i H_i)
-// is one fused pass (`lincomb`).
-#include "common.h"
+// is one fused pass (`lincomb`).  The slab-row store and the slab entry sum of `multi_dot` are
+// sweep_device.h's; every launch takes its resident-workgroup cap and grid from sweep_host.h.
+#include "sweep_device.h"
+#include "sweep_host.h"
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -103,20 +105,7 @@ __global__ __launch_bounds__(kDotThreads) void multi_dot_kernel(
       if (lane == 0) out[wid * K + k] = v;
     }
   } else {
-    __shared__ double scratch[8 * kDotWaves];
-#pragma unroll
-    for (int k0 = 0; k0 < K; k0 += 8) {
-      double v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = k0 + j < K ? (double)acc[(k0 + j) / NC][(k0 + j) % NC] : 0.0;
-      block_sum_n<8>(v, scratch);
-      if (threadIdx.x == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (k0 + j < K) out[k0 + j] = v[j];
-      }
-      __syncthreads();
-    }
+    slab_row_store<kDotThreads>(out, acc);
   }
 }
 
@@ -129,12 +118,10 @@ __global__ __launch_bounds__(kDotThreads) void multi_dot_reduce_kernel(
   const int t = blockIdx.x;
   const int r = t / nc, c = t % nc;
   const int g = r / rb, i = r % rb;
-  double s[1] = {0.0};
-  for (int b = threadIdx.x; b < nblk_x; b += kDotThreads)
-    s[0] += partial[((int64_t)b * ngroups + g) * rb * nc + i * nc + c];
-  __shared__ double scratch[kDotThreads / kWave];
-  block_sum_n<1>(s, scratch);
-  if (threadIdx.x == 0) out[t] = s[0];
+  const double s = slab_entry_sum<kDotThreads>(nblk_x, [&](int b) {
+    return partial[((int64_t)b * ngroups + g) * rb * nc + i * nc + c];
+  });
+  if (threadIdx.x == 0) out[t] = s;
 }
 
 // y = alpha * x + sum_i coef[i] * H[i, :]   (coef in device memory, nrows <= kLincombRows)
@@ -172,23 +159,12 @@ static void launch_dot(int64_t n, int gy, hipStream_t stream, bool vec, const fl
                        int nrows, const RowPtrs& rp, double* ws, int* bx_out) {
   auto kv = multi_dot_kernel<NC, RPW, SPLIT, true>;
   auto ks = multi_dot_kernel<NC, RPW, SPLIT, false>;
-  static int cap = 0;
-  if (cap == 0) {
-    int dev = 0, cus = 0, per = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kv, kDotThreads, 0);
-    cap = std::max(1, std::min(kDotMaxBlocks, std::max(1, cus) * std::max(1, per)));
-  }
-  const int64_t tpb = SPLIT ? kWave : kDotThreads;
-  const int64_t chunks = vec ? (n >> 2) : n;
-  const int bx = (int)std::max<int64_t>(1, std::min<int64_t>((chunks + tpb - 1) / tpb, cap));
+  static GridCap cap;  // of the 16-byte-load instantiation: one grid for both load paths
+  const int bx = chunk_grid(vec ? (n >> 2) : n, SPLIT ? kWave : kDotThreads,
+                            resident_cap(cap, kDotMaxBlocks, kDotThreads, kv));
   *bx_out = bx;
   dim3 grid(bx, gy);
-  if (vec)
-    hipLaunchKernelGGL(kv, grid, dim3(kDotThreads), 0, stream, a, lda, nrows, rp, n, ws);
-  else
-    hipLaunchKernelGGL(ks, grid, dim3(kDotThreads), 0, stream, a, lda, nrows, rp, n, ws);
+  hipLaunchKernelGGL(vec ? kv : ks, grid, dim3(kDotThreads), 0, stream, a, lda, nrows, rp, n, ws);
 }
 
 template <int NC>
@@ -230,9 +206,8 @@ void multi_dot(torch::Tensor A, int64_t nrows, std::vector<torch::Tensor> B, int
   auto stream = at::hip::getCurrentHIPStream();
   const float* a = A.data_ptr<float>();
   double* ws = workspace.data_ptr<double>();
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  bool vec = al16(a) && A.stride(0) % 4 == 0;
-  for (int64_t c = 0; c < nc; ++c) vec = vec && al16(rp.p[c]);
+  bool vec = aligned16(a) && A.stride(0) % 4 == 0;
+  for (int64_t c = 0; c < nc; ++c) vec = vec && aligned16(rp.p[c]);
   int bx = 1;
   const int64_t lda = A.stride(0);
   switch (nc) {
@@ -371,29 +346,10 @@ __global__ __launch_bounds__(256) void lincomb_cols_kernel(
 
 // Grid of a streaming pass: the chunk count capped at what the GPU holds resident at once
 // (as launch_dot), the rest by the grid-stride loop.  The cap is that of the instantiation
-// that is launched (the float4 and the scalar kernels differ in registers), kept per device.
-constexpr int kCapDevices = 64;
-struct GridCap {
-  int v[kCapDevices] = {};
-};
-
+// that is launched (the float4 and the scalar kernels differ in registers).
 template <typename K>
-static int resident_blocks(K kernel, GridCap& cap) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const bool keep = dev >= 0 && dev < kCapDevices;
-  if (keep && cap.v[dev] != 0) return cap.v[dev];
-  int cus = 0, per = 0;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, 256, 0);
-  const int c = std::max(1, std::min(kDotMaxBlocks, std::max(1, cus) * std::max(1, per)));
-  if (keep) cap.v[dev] = c;
-  return c;
-}
-
-static int stream_grid(int64_t n, bool vec, int cap) {
-  const int64_t chunks = vec ? (n >> 2) + (n & 3) : n;
-  return (int)std::max<int64_t>(1, std::min<int64_t>((chunks + 255) / 256, cap));
+static int stream_grid(int64_t n, bool vec, K kernel, GridCap& cap) {
+  return chunk_grid(sweep_chunks(n, vec), 256, resident_cap(cap, kDotMaxBlocks, 256, kernel));
 }
 
 template <int NC>
@@ -403,16 +359,10 @@ static void launch_lincomb_cols(bool vec, hipStream_t stream, const float* H, in
   static GridCap cap_v, cap_s;
   auto kv = lincomb_cols_kernel<NC, true>;
   auto ks = lincomb_cols_kernel<NC, false>;
-  const int blocks = stream_grid(n, vec, vec ? resident_blocks(kv, cap_v) : resident_blocks(ks, cap_s));
-  if (vec)
-    hipLaunchKernelGGL(kv, dim3(blocks), dim3(256), 0, stream, H, ldh, nrows, coef, alpha, cp,
-                       pre, post, n);
-  else
-    hipLaunchKernelGGL(ks, dim3(blocks), dim3(256), 0, stream, H, ldh, nrows, coef, alpha, cp,
-                       pre, post, n);
+  const int blocks = vec ? stream_grid(n, true, kv, cap_v) : stream_grid(n, false, ks, cap_s);
+  hipLaunchKernelGGL(vec ? kv : ks, dim3(blocks), dim3(256), 0, stream, H, ldh, nrows, coef,
+                     alpha, cp, pre, post, n);
 }
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 static const float* opt_vec(const c10::optional<torch::Tensor>& t, int64_t n, const char* what) {
   if (!t.has_value() || !t->defined()) return nullptr;
@@ -629,13 +579,9 @@ static void launch_diag_reg(bool vec, hipStream_t stream, const float* H, int64_
   static GridCap cap_v, cap_s;
   auto kv = compact_diag_reg_kernel<NR, true>;
   auto ks = compact_diag_reg_kernel<NR, false>;
-  const int blocks = stream_grid(n, vec, vec ? resident_blocks(kv, cap_v) : resident_blocks(ks, cap_s));
-  if (vec)
-    hipLaunchKernelGGL(kv, dim3(blocks), dim3(256), 0, stream, H, ldh, rows, fac, Q, k2, hrows, h0,
-                       scale, n, out);
-  else
-    hipLaunchKernelGGL(ks, dim3(blocks), dim3(256), 0, stream, H, ldh, rows, fac, Q, k2, hrows, h0,
-                       scale, n, out);
+  const int blocks = vec ? stream_grid(n, true, kv, cap_v) : stream_grid(n, false, ks, cap_s);
+  hipLaunchKernelGGL(vec ? kv : ks, dim3(blocks), dim3(256), 0, stream, H, ldh, rows, fac, Q, k2,
+                     hrows, h0, scale, n, out);
 }
 
 // H: [R, ldh] history; rows: [k2] int32 row of H per row of W; fac: [k2] fp32 factor per row;
@@ -673,7 +619,7 @@ void compact_diag(torch::Tensor H, torch::Tensor rows, torch::Tensor fac, torch:
     launch_diag_reg<40>(vec, stream, h, H.stride(0), rp, fp, qp, k, hr, h0f, sp, n, o);
   } else {
     static GridCap cap;
-    const int blocks = stream_grid(n, false, resident_blocks(compact_diag_tiled_kernel, cap));
+    const int blocks = stream_grid(n, false, compact_diag_tiled_kernel, cap);
     hipLaunchKernelGGL(compact_diag_tiled_kernel, dim3(blocks), dim3(256), 0, stream, h,
                        H.stride(0), rp, fp, qp, k, hr, h0f, sp, n, o);
   }

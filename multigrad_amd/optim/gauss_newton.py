@@ -56,13 +56,9 @@ from scipy.sparse.linalg import LinearOperator
 
 from ..ops.gram import weighted_gram
 from ..ops.lbfgs import MultiDot, compact_diag_, lincomb_, lincomb_cols_
-from ..utils.hooks import driver_guard
-from ..utils.progress import trange
+from ._damped import LAMBDA_MIN, damped_loop
 
 __all__ = ["run_gauss_newton", "run_gauss_newton_dual", "dual_step", "GaussNewtonInvProduct"]
-
-_LAMBDA_MIN, _LAMBDA_MAX = 1e-12, 1e12
-
 
 def _scalar(loss) -> float:
     if isinstance(loss, (tuple, list)):
@@ -104,7 +100,7 @@ def run_gauss_newton(gauss_newton_fn: Callable, loss_fn: Callable, params, maxst
     -------
     scipy.optimize.OptimizeResult, identical on every rank: ``x``, ``fun``, ``jac``, ``nit``,
     ``nfev``, ``njev``, ``success``, ``message``, ``jac_mode`` (``"forward"`` or
-    ``"reverse"``, the Jacobian mode actually used) and ``hess_inv``, the float64
+    ``"reverse"``, the Jacobian mode of the last evaluation) and ``hess_inv``, the float64
     pseudo-inverse of the final Gauss-Newton matrix.
     """
     x_t = torch.as_tensor(params).detach()
@@ -114,50 +110,21 @@ def run_gauss_newton(gauss_newton_fn: Callable, loss_fn: Callable, params, maxst
     def tensor(v):
         return torch.as_tensor(v, dtype=dtype, device=device).reshape(shape)
 
-    lam = float(damping)
-    nit = nfev = njev = 0
-    success, message, jac_mode = False, "maximum number of iterations reached", None
-    with driver_guard(comm):
-        bar = trange(maxsteps, desc="Gauss-Newton Progress")
-        steps = iter(bar)
-        loss = g = G = None
-        while True:
-            out = gauss_newton_fn(tensor(x))
-            njev += 1
-            jac_mode = out[3]
-            loss, g, G = _scalar(out[0]), _host(out[1]).reshape(-1), _host(out[2])
-            if not g.size or np.max(np.abs(g)) <= gtol:
-                success, message = True, "converged: max |grad| <= gtol"
-                break
-            if next(steps, None) is None:
-                break
-            accepted = None
-            while lam <= _LAMBDA_MAX:
-                trial = x + _solve(G, lam, g)
-                new = _scalar(loss_fn(tensor(trial)))
-                nfev += 1
-                if np.isfinite(new) and new < loss:
-                    accepted = new
-                    break
-                lam *= 10.0
-            if accepted is None:
-                message = "no step reduced the loss (damping above 1e12)"
-                break
-            x = trial
-            lam = max(lam / 10.0, _LAMBDA_MIN)
-            nit += 1
-            if (loss - accepted) / max(abs(loss), abs(accepted), 1.0) <= ftol:
-                # the state below belongs to the accepted point
-                out = gauss_newton_fn(tensor(x))
-                njev += 1
-                loss, g, G = _scalar(out[0]), _host(out[1]).reshape(-1), _host(out[2])
-                success, message = True, "converged: relative loss decrease <= ftol"
-                break
-        if hasattr(bar, "close"):
-            bar.close()
+    def evaluate(xv):
+        out = gauss_newton_fn(tensor(xv))
+        return _scalar(out[0]), (_host(out[1]).reshape(-1), _host(out[2]), out[3])
+
+    run = damped_loop(
+        x, evaluate, finite=lambda state: True,
+        converged=lambda state, xv: not state[0].size or np.max(np.abs(state[0])) <= gtol,
+        measure="max |grad|",
+        trials=lambda state, xv: lambda lam: xv + _solve(state[1], lam, state[0]),
+        loss_at=lambda trial: _scalar(loss_fn(tensor(trial))),
+        maxsteps=maxsteps, damping=damping, floor=LAMBDA_MIN, ftol=ftol, comm=comm)
+    g, G, jac_mode = run.state
     return scipy.optimize.OptimizeResult(
-        x=x.reshape(shape), fun=loss, jac=g.reshape(shape), nit=nit, nfev=nfev, njev=njev,
-        success=success, message=message, jac_mode=jac_mode,
+        x=run.x.reshape(shape), fun=run.loss, jac=g.reshape(shape), nit=run.nit, nfev=run.nfev,
+        njev=run.njev, success=run.success, message=run.message, jac_mode=jac_mode,
         hess_inv=np.linalg.pinv(G) if G.size else G)
 
 
@@ -385,6 +352,16 @@ class GaussNewtonInvProduct(LinearOperator):
         return Jh.T @ self.C @ Jh
 
 
+def _factors(factors_fn: Callable, x: torch.Tensor, shape, copies: list):
+    """One call of a dual driver's ``factors_fn`` at the flat ``x`` as the frame's
+    ``(loss, state)``, the state being ``(_DualFactors, jac_mode)``."""
+    out = factors_fn(x.reshape(shape))
+    K = torch.as_tensor(out[1]).numel()
+    J = torch.as_tensor(out[2]).detach().reshape(K, x.numel())
+    J = J.to(device=x.device, dtype=x.dtype)
+    return _scalar(out[0]), (_DualFactors(J, out[1], out[3], copies), out[4])
+
+
 def run_gauss_newton_dual(factors_fn: Callable, loss_fn: Callable, params, maxsteps: int = 50,
                           damping: float = 1e-3, ftol: float = 2.2e-9, gtol: float = 1e-8,
                           comm=None):
@@ -414,60 +391,17 @@ def run_gauss_newton_dual(factors_fn: Callable, loss_fn: Callable, params, maxst
     x = x_t.reshape(-1).clone()
     copies: list = []
 
-    def factors(xv):
-        out = factors_fn(xv.reshape(shape))
-        K = torch.as_tensor(out[1]).numel()
-        J = torch.as_tensor(out[2]).detach().reshape(K, xv.numel())
-        J = J.to(device=xv.device, dtype=xv.dtype)
-        return _scalar(out[0]), _DualFactors(J, out[1], out[3], copies), out[4]
-
-    lam = float(damping)
-    nit = nfev = njev = 0
-    success, message, jac_mode = False, "maximum number of iterations reached", None
-    with driver_guard(comm):
-        bar = trange(maxsteps, desc="Gauss-Newton Progress")
-        steps = iter(bar)
-        loss = fac = None
-        while True:
-            fac = None   # at most one Jacobian alive
-            loss, fac, jac_mode = factors(x)
-            njev += 1
-            if not fac.finite:
-                message = "the Jacobian or the loss derivatives are not finite at the current point"
-                break
-            if not fac.P or fac.gmax <= gtol:
-                success, message = True, "converged: max |grad| <= gtol"
-                break
-            if next(steps, None) is None:
-                break
-            accepted = trial = None
-            while lam <= _LAMBDA_MAX:
-                trial = x + fac.step(lam)
-                new = _scalar(loss_fn(trial.reshape(shape)))
-                nfev += 1
-                if np.isfinite(new) and new < loss:
-                    accepted = new
-                    break
-                lam *= 10.0
-            if accepted is None:
-                message = "no step reduced the loss (damping above 1e12)"
-                break
-            x = trial
-            lam = max(lam / 10.0, _LAMBDA_MIN)
-            nit += 1
-            if (loss - accepted) / max(abs(loss), abs(accepted), 1.0) <= ftol:
-                # the state below belongs to the accepted point
-                fac = None
-                loss, fac, jac_mode = factors(x)
-                njev += 1
-                success, message = True, "converged: relative loss decrease <= ftol"
-                if not fac.finite:
-                    success = False
-                    message = "the Jacobian or the loss derivatives are not finite at the current point"
-                break
-        if hasattr(bar, "close"):
-            bar.close()
+    run = damped_loop(
+        x, lambda xv: _factors(factors_fn, xv, shape, copies),
+        finite=lambda state: state[0].finite,
+        converged=lambda state, xv: not state[0].P or state[0].gmax <= gtol,
+        measure="max |grad|",
+        trials=lambda state, xv: lambda lam: xv + state[0].step(lam),
+        loss_at=lambda trial: _scalar(loss_fn(trial.reshape(shape))),
+        maxsteps=maxsteps, damping=damping, floor=LAMBDA_MIN, ftol=ftol, comm=comm)
+    fac, jac_mode = run.state
     return scipy.optimize.OptimizeResult(
-        x=x.reshape(shape), fun=loss, jac=fac.g.reshape(shape), nit=nit, nfev=nfev, njev=njev,
-        success=success, message=message, jac_mode=jac_mode, solver="dual",
-        hess_inv=GaussNewtonInvProduct(fac.J, fac.L), host_copy_sizes=copies)
+        x=run.x.reshape(shape), fun=run.loss, jac=fac.g.reshape(shape), nit=run.nit,
+        nfev=run.nfev, njev=run.njev, success=run.success, message=run.message,
+        jac_mode=jac_mode, solver="dual", hess_inv=GaussNewtonInvProduct(fac.J, fac.L),
+        host_copy_sizes=copies)

@@ -54,9 +54,8 @@ import scipy.optimize
 import torch
 
 from ..ops.box_dual import box_dual_pass
-from ..utils.hooks import driver_guard
-from ..utils.progress import trange
-from .gauss_newton import _LAMBDA_MAX, GaussNewtonInvProduct, _DualFactors, _scalar
+from ._damped import damped_loop
+from .gauss_newton import GaussNewtonInvProduct, _DualFactors, _factors, _scalar
 from .transforms import Bounds
 
 __all__ = ["run_gauss_newton_box", "box_step", "BoxSolve"]
@@ -227,14 +226,7 @@ def run_gauss_newton_box(factors_fn: Callable, loss_fn: Callable, params, param_
     copies: list = []
     trials: list = []
 
-    def factors(xv):
-        out = factors_fn(xv.reshape(shape))
-        K = torch.as_tensor(out[1]).numel()
-        J = torch.as_tensor(out[2]).detach().reshape(K, xv.numel())
-        J = J.to(device=xv.device, dtype=xv.dtype)
-        return _scalar(out[0]), _DualFactors(J, out[1], out[3], copies), out[4]
-
-    def projected_gradient(g):
+    def projected_gradient(g, x):
         if not P:
             return 0.0
         copies.append(1)
@@ -242,74 +234,41 @@ def run_gauss_newton_box(factors_fn: Callable, loss_fn: Callable, params, param_
         # below half a unit in the last place of x would otherwise vanish in x - g
         return float(torch.clamp(-g, min=l - x, max=u - x).abs().max())
 
-    lam = max(float(damping), float(min_damping))
-    floor = float(min_damping)
-    nit = nfev = njev = npasses = unconverged = 0
-    success, message, jac_mode = False, "maximum number of iterations reached", None
-    not_finite = "the Jacobian or the loss derivatives are not finite at the current point"
-    with driver_guard(comm):
-        bar = trange(maxsteps, desc="Gauss-Newton Progress")
-        steps = iter(bar)
-        loss = fac = None
-        delta = torch.zeros(P, dtype=dt, device=dev)
-        while True:
-            fac = None   # at most one Jacobian alive
-            loss, fac, jac_mode = factors(x)
-            njev += 1
-            if not fac.finite:
-                message = not_finite
-                break
-            if not fac.P or projected_gradient(fac.g) <= gtol:
-                success, message = True, "converged: max |projected grad| <= gtol"
-                break
-            if next(steps, None) is None:
-                break
-            lo = l - x if cap is None else torch.maximum(l - x, -cap)
-            hi = u - x if cap is None else torch.minimum(u - x, cap)
-            lo, hi = lo.clamp_(max=0.0), hi.clamp_(min=0.0)
-            d = _scaling(fac) if fac.dmax > 0.0 else None
-            accepted = trial = None
-            while lam <= _LAMBDA_MAX:
-                if d is None:   # J^T H+ J = 0: no step, as in the dual driver
-                    delta.zero_()
-                    trials.append((lam, 0, True, False))
-                else:
-                    sol = _solve_box(fac, d, lo, hi, lam, delta, int(inner_passes), copies)
-                    npasses += sol.passes
-                    if not sol.converged:
-                        unconverged += 1
-                        trials.append((lam, sol.passes, False, False))
-                        lam *= 10.0
-                        floor = max(floor, lam)
-                        continue
-                    trials.append((lam, sol.passes, True, False))
-                trial = torch.clamp(x + delta, min=l, max=u)
-                # a step that the bound itself limits ends on the bound, not an ulp inside
-                trial = torch.where(delta <= l - x, l, torch.where(delta >= u - x, u, trial))
-                new = _scalar(loss_fn(trial.reshape(shape)))
-                nfev += 1
-                if np.isfinite(new) and new < loss:
-                    accepted = new
-                    trials[-1] = trials[-1][:3] + (True,)
-                    break
-                lam *= 10.0
-            if accepted is None:
-                message = "no step reduced the loss (damping above 1e12)"
-                break
-            x = trial
-            lam = max(lam / 10.0, floor)
-            nit += 1
-            if (loss - accepted) / max(abs(loss), abs(accepted), 1.0) <= ftol:
-                # the state below belongs to the accepted point
-                fac = None
-                loss, fac, jac_mode = factors(x)
-                njev += 1
-                success, message = True, "converged: relative loss decrease <= ftol"
-                if not fac.finite:
-                    success, message = False, not_finite
-                break
-        if hasattr(bar, "close"):
-            bar.close()
+    delta = torch.zeros(P, dtype=dt, device=dev)
+
+    def trials_from(state, x):
+        fac = state[0]
+        lo = l - x if cap is None else torch.maximum(l - x, -cap)
+        hi = u - x if cap is None else torch.minimum(u - x, cap)
+        lo, hi = lo.clamp_(max=0.0), hi.clamp_(min=0.0)
+        d = _scaling(fac) if fac.dmax > 0.0 else None
+
+        def propose(lam):
+            if d is None:   # J^T H+ J = 0: no step, as in the dual driver
+                delta.zero_()
+                trials.append((lam, 0, True, False))
+            else:
+                sol = _solve_box(fac, d, lo, hi, lam, delta, int(inner_passes), copies)
+                trials.append((lam, sol.passes, sol.converged, False))
+                if not sol.converged:
+                    return None
+            trial = torch.clamp(x + delta, min=l, max=u)
+            # a step that the bound itself limits ends on the bound, not an ulp inside
+            return torch.where(delta <= l - x, l, torch.where(delta >= u - x, u, trial))
+        return propose
+
+    def accept():
+        trials[-1] = trials[-1][:3] + (True,)
+
+    run = damped_loop(
+        x, lambda xv: _factors(factors_fn, xv, shape, copies),
+        finite=lambda state: state[0].finite,
+        converged=lambda state, xv: not P or projected_gradient(state[0].g, xv) <= gtol,
+        measure="max |projected grad|", trials=trials_from,
+        loss_at=lambda trial: _scalar(loss_fn(trial.reshape(shape))),
+        maxsteps=maxsteps, damping=max(float(damping), float(min_damping)), floor=min_damping,
+        ftol=ftol, comm=comm, on_accept=accept)
+    (fac, jac_mode), x = run.state, run.x
     g = fac.g
     fixed = l == u
     lower = (x <= l) & ((g > 0) | fixed)
@@ -319,8 +278,8 @@ def run_gauss_newton_box(factors_fn: Callable, loss_fn: Callable, params, param_
     if P and bool(active.any()):
         Jm.mul_((active == 0).to(Jm.dtype))
     return scipy.optimize.OptimizeResult(
-        x=x.reshape(shape), fun=loss, jac=g.reshape(shape), nit=nit, nfev=nfev, njev=njev,
-        success=success, message=message, jac_mode=jac_mode, solver="dual-box",
-        hess_inv=GaussNewtonInvProduct(Jm, fac.L), host_copy_sizes=copies,
-        inner_passes=npasses, inner_unconverged=unconverged, active=active.reshape(shape),
-        damping=lam, damping_floor=floor, trials=trials)
+        x=x.reshape(shape), fun=run.loss, jac=g.reshape(shape), nit=run.nit, nfev=run.nfev,
+        njev=run.njev, success=run.success, message=run.message, jac_mode=jac_mode,
+        solver="dual-box", hess_inv=GaussNewtonInvProduct(Jm, fac.L), host_copy_sizes=copies,
+        inner_passes=sum(t[1] for t in trials), inner_unconverged=sum(not t[2] for t in trials),
+        active=active.reshape(shape), damping=run.damping, damping_floor=run.floor, trials=trials)
