@@ -3,7 +3,8 @@
 Same public API as AlanPearl/multigrad (reference ``multigrad/__init__.py:1-9``):
 ``OnePointModel``, ``OnePointGroup``, ``reduce_sum``, ``split_subcomms``,
 ``split_subcomms_by_node``, ``util`` and ``__version__``; plus ``adam``/``bfgs`` optimizer
-modules, the communicator layer and the fused device engine.
+modules, ``GaussianPrior`` (parameter priors for ``run_bfgs`` and ``run_hmc``), the
+communicator layer and the fused device engine.
 """
 from ._version import __version__  # noqa: F401
 from .models.onepoint import OnePointModel, OnePointGroup
@@ -12,10 +13,11 @@ from .parallel.comm import get_world_comm, init_distributed
 from .utils import util
 from . import parallel
 from .optim import adam, bfgs
+from .optim.prior import GaussianPrior
 
 __all__ = ["OnePointModel", "OnePointGroup", "reduce_sum", "split_subcomms",
            "split_subcomms_by_node", "util", "adam", "bfgs", "get_world_comm",
-           "init_distributed", "__version__"]
+           "init_distributed", "GaussianPrior", "__version__"]
 
 
 def __getattr__(name):

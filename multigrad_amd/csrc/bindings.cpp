@@ -147,6 +147,16 @@ void hmc_momentum(torch::Tensor z, torch::Tensor inv_mass, torch::Tensor p,
 void hmc_commit(torch::Tensor q, int64_t count, c10::optional<torch::Tensor> mean,
                 c10::optional<torch::Tensor> m2, c10::optional<torch::Tensor> track_idx,
                 c10::optional<torch::Tensor> track_row, c10::optional<torch::Tensor> sample_row);
+
+// prior.hip
+int64_t prior_workspace();
+void gaussian_prior_grad(torch::Tensor x, torch::Tensor g, torch::Tensor mean,
+                         torch::Tensor inv_var, double c, torch::Tensor out,
+                         c10::optional<torch::Tensor> pen_out, c10::optional<torch::Tensor> ws);
+void hmc_leapfrog_prior(torch::Tensor q, torch::Tensor p, torch::Tensor g, torch::Tensor inv_mass,
+                        double a, double b, torch::Tensor mean, torch::Tensor inv_var, double ap,
+                        c10::optional<torch::Tensor> ke_out, c10::optional<torch::Tensor> pen_out,
+                        c10::optional<torch::Tensor> ws);
 // binned.hip
 torch::Tensor binned_forward(torch::Tensor mu, torch::Tensor sigma, c10::optional<torch::Tensor> w,
                              std::vector<double> edges);
@@ -306,6 +316,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("hmc_leapfrog", &mg::hmc_leapfrog);
   m.def("hmc_momentum", &mg::hmc_momentum);
   m.def("hmc_commit", &mg::hmc_commit);
+  m.def("prior_workspace", &mg::prior_workspace);
+  m.def("gaussian_prior_grad", &mg::gaussian_prior_grad);
+  m.def("hmc_leapfrog_prior", &mg::hmc_leapfrog_prior);
   m.def("binned_forward", &mg::binned_forward);
   m.def("binned_backward", &mg::binned_backward);
   m.def("binned_backward2", &mg::binned_backward2);

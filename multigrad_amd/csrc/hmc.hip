@@ -17,56 +17,19 @@
 // pointers 16-byte aligned) or as guarded scalars (any other view, and the last partial
 // chunk), and the grid is the same for both, so the energies are bitwise equal on both
 // load paths and from run to run for a fixed n and device.  The elementwise updates are
-// written with explicit fmaf, the same on both paths.  The final sum is sweep_device.h's slab
-// entry sum; the cap over a kernel family and the grid are sweep_host.h's.
+// written with explicit fmaf, the same on both paths.  The chunk load and store, the slab row
+// and the grid are chunk_sweep.h's (shared with prior.hip); the final sum is sweep_device.h's
+// slab entry sum and the cap over a kernel family sweep_host.h's.
 //
 // gfx950 (hipcc -O3), VGPRs per instantiation <VEC, BCAST>; no scratch, 8 waves per SIMD:
 //   hmc_leapfrog_kernel  <1,0> 30  <1,1> 30  <0,0> 30  <0,1> 30
 //   hmc_momentum_kernel  <1,0> 25  <1,1> 22  <0,0> 25  <0,1> 21
 //   hmc_commit_kernel    <1> 33    <0> 30      hmc_reduce_kernel 18
-#include "sweep_device.h"
-#include "sweep_host.h"
+#include "chunk_sweep.h"
 
-#include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
 namespace mg {
-
-constexpr int kHmcThreads = 256;
-constexpr int kHmcMaxBlocks = 2048;  // slab rows of the workspace
-
-// the cnt <= 4 elements of the chunk at off: one float4 when VEC and the chunk is whole
-template <bool VEC>
-__device__ __forceinline__ void load_chunk(const float* __restrict__ x, int64_t off, int cnt,
-                                           float (&v)[4]) {
-  if (VEC && cnt == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(x + off);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = e < cnt ? x[off + e] : 0.0f;
-  }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store_chunk(float* __restrict__ x, int64_t off, int cnt,
-                                            const float (&v)[4]) {
-  if (VEC && cnt == 4) {
-    *reinterpret_cast<float4*>(x + off) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (e < cnt) x[off + e] = v[e];
-  }
-}
-
-// the workgroup's sum into its slab row (every thread of the workgroup calls it)
-__device__ __forceinline__ void slab_row(double acc, double* __restrict__ partial) {
-  __shared__ double scratch[kHmcThreads / kWave];
-  double s[1] = {acc};
-  block_sum_n<1>(s, scratch);
-  if (threadIdx.x == 0) partial[blockIdx.x] = s[0];
-}
 
 template <bool VEC, bool BCAST>
 __global__ __launch_bounds__(kHmcThreads) void hmc_leapfrog_kernel(
@@ -184,21 +147,6 @@ __global__ __launch_bounds__(kHmcThreads) void hmc_commit_kernel(
   }
 }
 
-// Grid of a pass: the chunk count capped at what the GPU holds resident at once (as
-// launch_dot / the streaming passes of lbfgs.hip).  One cap per kernel family -- the least
-// of its instantiations -- so the float4 and the scalar path launch the same grid and sum
-// their energies in the same order.
-template <typename... K>
-static int hmc_grid(int64_t n, GridCap& cap, K... kernels) {
-  return chunk_grid((n + 3) >> 2, kHmcThreads,
-                    resident_cap(cap, kHmcMaxBlocks, kHmcThreads, kernels...));
-}
-
-static void check_vec(const torch::Tensor& t, int64_t n, const char* what) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == n,
-              what, ": contiguous fp32 device vector of n elements");
-}
-
 // inv_mass: n elements, or 1 (broadcast)
 static bool check_mass(const torch::Tensor& m, int64_t n) {
   TORCH_CHECK(m.is_cuda() && m.scalar_type() == at::kFloat && m.is_contiguous() &&
@@ -295,8 +243,6 @@ void hmc_momentum(torch::Tensor z, torch::Tensor inv_mass, torch::Tensor p,
     hipLaunchKernelGGL(hmc_reduce_kernel, dim3(1), dim3(kHmcThreads), 0, stream, partial, blocks,
                        out);
 }
-
-static bool has(const c10::optional<torch::Tensor>& t) { return t.has_value() && t->defined(); }
 
 void hmc_commit(torch::Tensor q, int64_t count, c10::optional<torch::Tensor> mean,
                 c10::optional<torch::Tensor> m2, c10::optional<torch::Tensor> track_idx,

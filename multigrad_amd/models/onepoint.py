@@ -156,7 +156,8 @@ class _OptimizerFrontEnds:
                               randkey=randkey, comm=comm, **kw)
 
     def run_bfgs(self, guess, maxsteps: int = 100, param_bounds=None, randkey=None,
-                 comm=None, method: str = "auto", hess_inv: bool = True, **kw):
+                 comm=None, method: str = "auto", hess_inv: bool = True, prior=None,
+                 prior_weight: float = 1.0, **kw):
         """L-BFGS(-B); returns a ``scipy.optimize.OptimizeResult`` on every rank.
 
         ``method="scipy"``: scipy's L-BFGS-B on the root rank, other ranks serve its
@@ -174,9 +175,19 @@ class _OptimizerFrontEnds:
         sharded runs).  It holds the optimizer's history ring on the device without a copy
         (``2 (history + 1)`` fp32 vectors: 0.9 GB at 1e7 parameters); ``hess_inv=False`` frees
         the ring on return.  ``method="scipy"`` always returns scipy's own operator.
+
+        ``prior`` (a :class:`~multigrad_amd.optim.prior.GaussianPrior` on the parameters
+        themselves, in every bounds mode) minimises ``loss + prior_weight * prior.penalty(x)``;
+        ``prior_weight = 1 / loss_scale`` gives the MAP of the posterior that
+        ``run_hmc(prior=prior, loss_scale=loss_scale)`` samples.  ``res.fun`` is the minimised
+        objective, ``res.prior_penalty`` the unweighted penalty at ``res.x``, and
+        ``res.hess_inv`` approximates the inverse Hessian of likelihood plus prior.
         """
+        from ..optim.prior import PriorObjective, check_prior, penalised_function, with_penalty
         comm = self._opt_comm() if comm is None else comm
         x0 = as_param_tensor(guess, device=self.param_device())
+        check_prior(prior, x0.numel())  # before any collective
+        pkw = {} if prior is None else {"prior": prior, "prior_weight": prior_weight}
         if method == "auto":
             method = "device" if x0.numel() > 100_000 else "scipy"
         if method == "scipy":
@@ -193,10 +204,12 @@ class _OptimizerFrontEnds:
                 eng = GraphAdamEngine(self, comm=comm)
                 fn = eng.evaluator(x0, randkey=None if randkey is None else init_randkey(randkey)
                                    if not hasattr(randkey, "split") else randkey)
+            if prior is not None:  # on every rank: the workers serve the same function
+                fn = penalised_function(fn, prior, prior_weight)
             try:
-                return _bfgs.run_bfgs(fn, x0, maxsteps=maxsteps,
-                                      param_bounds=param_bounds, randkey=randkey, comm=comm,
-                                      device=self.param_device(), **kw)
+                return with_penalty(_bfgs.run_bfgs(
+                    fn, x0, maxsteps=maxsteps, param_bounds=param_bounds, randkey=randkey,
+                    comm=comm, device=self.param_device(), **kw), prior)
             finally:
                 if eng is not None:
                     eng.close()
@@ -213,25 +226,32 @@ class _OptimizerFrontEnds:
             if eng is not None:
                 try:
                     obj = eng.lbfgs_objective(x0)
+                    if prior is not None:
+                        obj = PriorObjective(obj, prior, prior_weight)
                     if param_bounds is None:
-                        return _lbfgs.lbfgs_minimize(obj, maxiter=maxsteps, m=hist, **kw)
+                        return with_penalty(
+                            _lbfgs.lbfgs_minimize(obj, maxiter=maxsteps, m=hist, **kw), prior)
                     lo, hi = obj.local_box(param_bounds)
-                    return _lbfgsb.lbfgsb_minimize(obj, lo, hi, maxiter=maxsteps, m=hist, **kw)
+                    return with_penalty(_lbfgsb.lbfgsb_minimize(
+                        obj, lo, hi, maxiter=maxsteps, m=hist, **kw), prior)
                 finally:
                     if not getattr(eng, "cached", False):
                         eng.close()
         if param_bounds is not None and mode == "project":
             return _lbfgsb.run_lbfgsb_device(self.calc_loss_and_grad_from_params, x0,
                                              maxsteps=maxsteps, param_bounds=param_bounds,
-                                             randkey=randkey, comm=comm, history=hist, **kw)
+                                             randkey=randkey, comm=comm, history=hist, **pkw,
+                                             **kw)
         return _lbfgs.run_lbfgs_device(self.calc_loss_and_grad_from_params, x0, maxsteps=maxsteps,
                                        param_bounds=param_bounds, randkey=randkey, comm=comm,
-                                       history=hist, **kw)
+                                       history=hist, **pkw, **kw)
 
     def run_hmc(self, guess, nsamples: int = 1000, warmup: int = 500, nleapfrog: int = 10,
                 step_size: float = 0.1, param_bounds=None, randkey=0, loss_scale: float = 1.0,
-                history: str = "full", track=None, comm=None, **kw):
-        """Draw from the posterior ``exp(-loss_scale * loss)`` by Hamiltonian Monte Carlo
+                history: str = "full", track=None, comm=None, prior=None, **kw):
+        """Draw from the posterior ``exp(-loss_scale * loss)`` -- with ``prior``, a
+        :class:`~multigrad_amd.optim.prior.GaussianPrior`,
+        ``exp(-(loss_scale * loss + prior.penalty(x)))`` -- by Hamiltonian Monte Carlo
         (:mod:`multigrad_amd.optim.hmc`); returns an
         :class:`~multigrad_amd.optim.hmc.HMCResult` on every rank.
 
@@ -241,7 +261,11 @@ class _OptimizerFrontEnds:
         returns ``samples [nsamples, P]``; ``history="moments"`` only ``mean`` and ``var``
         (with ``track=indices`` for the chains of a few parameters: the intended use at 1e7
         parameters).  With ``param_bounds`` the chain runs in the unbounded coordinates of
-        :mod:`~multigrad_amd.optim.transforms` with a flat prior on the bounded parameters.
+        :mod:`~multigrad_amd.optim.transforms` with a flat prior on the bounded parameters
+        unless ``prior`` is given.  The prior is on the bounded parameters and is a density: it
+        is not scaled by ``loss_scale``, so the MAP of the sampled posterior is
+        ``run_bfgs(prior=prior, prior_weight=1 / loss_scale)``.  On the engine path its force
+        and its energy come out of the fused leapfrog pass (``csrc/prior.hip``).
         Models with the fused-engine protocol (and no bounds) sample over the engine's
         (ZeRO- or owner-) sharded vectors, the evaluations of a trajectory staying on the
         device; everything else goes through ``calc_loss_and_grad_from_params``.  Extra
@@ -249,11 +273,15 @@ class _OptimizerFrontEnds:
         ``adapt_mass``, ``inv_mass``) go to :func:`multigrad_amd.optim.hmc.hmc_sample`."""
         from ..optim import hmc as _hmc
         from ..optim.lbfgs import GenericObjective
+        from ..optim.prior import check_prior
         from ..optim.transforms import Bounds
         comm = self._opt_comm() if comm is None else comm
         x0 = as_param_tensor(guess, device=self.param_device())
+        check_prior(prior, x0.numel())  # before any collective
         skw = dict(nsamples=nsamples, warmup=warmup, nleapfrog=nleapfrog, step_size=step_size,
                    loss_scale=loss_scale, seed=randkey, history=history, track=track)
+        if prior is not None:
+            skw["prior"] = prior
         fused = getattr(self, "fused_engine", None)
         if fused is not None and param_bounds is None:
             eng = fused(comm=comm, **{k: kw.pop(k) for k in ("zero", "chunks") if k in kw})

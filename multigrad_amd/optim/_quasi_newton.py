@@ -175,20 +175,32 @@ class TrialPoints:
 
     ``sums`` must not refer to the run or to this object: a reference cycle would keep the
     run's device vectors (the ring among them) alive until the next garbage collection
-    instead of freeing them when the driver returns."""
+    instead of freeing them when the driver returns.
+
+    Optional protocol: an objective whose loss has a term that is a per-rank partial sum (the
+    penalty of :class:`~multigrad_amd.optim.prior.PriorObjective` on sharded vectors) offers
+    ``partial_call(x, device=False) -> (loss, grad, partial)`` with ``partial`` a 1-element
+    fp64 device tensor.  It then rides behind the partial sums above in the same reduction and
+    copy, and its sum over the ranks completes the loss.  An objective without
+    ``partial_call`` takes the path described first."""
 
     def __init__(self, obj, red, device):
         self.obj, self.red = obj, red
         self.dev_call = getattr(obj, "device_call", None) if device.type == "cuda" else None
+        self.partial = getattr(obj, "partial_call", None)
         self.nfev = 0
         self.xt = None
         self.cache: dict = {}
 
     def initial(self, x: torch.Tensor):
         """``(f, g)`` at the start point."""
-        f, g = self.obj(x)
         self.nfev += 1
         self.xt = torch.empty_like(x)
+        if self.partial is not None:
+            f, g, part = self.partial(x)
+            g = g.clone()
+            return f + float(self.red.reduce(sums=[part])[0]), g
+        f, g = self.obj(x)
         return f, g.clone()
 
     def start(self, x, d, sums) -> None:
@@ -198,7 +210,18 @@ class TrialPoints:
     def __call__(self, alpha):
         torch.add(self.x, self.d, alpha=float(alpha), out=self.xt)
         first = not self.cache
-        if self.dev_call is not None:
+        if self.partial is not None:
+            dev = self.dev_call is not None
+            lt, ga, part = self.partial(self.xt, device=dev)
+            ga = ga.clone()
+            sums = list(self.sums(ga, first)) + [part]
+            if dev:
+                h = self.red.reduce(sums=sums, local=[lt.reshape(1)])
+                fa, h = float(h[-1]) + float(h[-2]), h[:-2]
+            else:
+                h = self.red.reduce(sums=sums)
+                fa, h = lt + float(h[-1]), h[:-1]
+        elif self.dev_call is not None:
             lt, ga = self.dev_call(self.xt)
             ga = ga.clone()
             h = self.red.reduce(sums=self.sums(ga, first), local=[lt.reshape(1)])

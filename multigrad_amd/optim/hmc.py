@@ -33,6 +33,17 @@ matrix); this module draws from the posterior itself.  The potential is
   :mod:`~multigrad_amd.optim.transforms` with a flat prior on the bounded parameter:
   ``U(u) = loss_scale * loss(x(u)) - sum log dp/du``.  Samples, ``mean`` and ``var`` are in the
   bounded parameters.
+* **Prior** (``prior=``, a :class:`~multigrad_amd.optim.prior.GaussianPrior`): the chain draws
+  from ``exp(-(loss_scale * loss + pen))`` -- the prior is a density and is not scaled by
+  ``loss_scale``, so the MAP of this posterior is
+  ``run_bfgs(prior=..., prior_weight=1 / loss_scale)``.  ``g`` stays the gradient of the loss
+  (the cached one included): every leapfrog launch is ``hmc_leapfrog_prior_``
+  (``csrc/prior.hip``), which takes the prior's force from the position it reads, and the
+  launch that ends a trajectory also sums the penalty there, so ``[K, K', pen']`` travel in
+  the one reduction and ``U' = loss_scale * loss' + pen'`` comes out of the same single copy.
+  With bounds the prior is folded into the wrapped function in ``x`` before the chain rule:
+  ``U(u) = loss_scale * loss(x(u)) + pen(x(u)) - sum log dp/du``.  ``prior=None`` runs the
+  code without any of this.
 """
 from __future__ import annotations
 
@@ -44,6 +55,7 @@ import scipy.optimize
 import torch
 
 from ..ops.hmc import hmc_commit_, hmc_leapfrog_, hmc_momentum_, hmc_workspace
+from ..ops.prior import gaussian_prior_grad_, hmc_leapfrog_prior_, prior_workspace
 from ..utils.random import PRNGKey, init_randkey
 from ._quasi_newton import driver, finish
 from ._reduce import DeviceReducer
@@ -61,7 +73,7 @@ class HMCResult(scipy.optimize.OptimizeResult):
     ``[nsamples, len(track)]`` (or ``None``), ``mean`` / ``var`` ``[P]`` of the draws (``var``
     with ``ddof = 1``), ``x`` the last position, ``potential`` ``[nsamples]`` (numpy, ``U`` of
     every draw), ``accept_rate`` (of the sampling iterations; of the warm-up when
-    ``nsamples = 0``), ``step_size``, ``inv_mass`` (one element while no mass was adapted or
+    ``nsamples = 0``; with a prior ``U`` includes the penalty), ``step_size``, ``inv_mass`` (one element while no mass was adapted or
     given per parameter), ``n_divergent`` (of the sampling iterations; the warm-up's, which
     dual averaging provokes while it explores steps up to ten times the initial one, are
     ``n_divergent_warmup``), ``nfev``, ``warmup_windows``."""
@@ -162,8 +174,9 @@ def hmc_sample(obj, nsamples: int = 1000, warmup: int = 500, nleapfrog: int = 10
                step_size: float = 0.1, loss_scale: float = 1.0, jitter: float = 0.0,
                seed=0, noise=None, target_accept: float = 0.8, adapt_step_size: bool = True,
                adapt_mass: bool = True, inv_mass=None, history: str = "full",
-               track=None) -> HMCResult:
-    """Sample ``exp(-loss_scale * loss)`` over ``obj`` (the objective interface of the device
+               track=None, prior=None) -> HMCResult:
+    """Sample ``exp(-loss_scale * loss)`` -- with ``prior``,
+    ``exp(-(loss_scale * loss + prior.penalty(x)))`` -- over ``obj`` (the objective interface of the device
     L-BFGS: :class:`~multigrad_amd.optim.lbfgs.GenericObjective`, the engine objective) by
     HMC; see the module docstring for the algorithm.
 
@@ -183,6 +196,9 @@ def hmc_sample(obj, nsamples: int = 1000, warmup: int = 500, nleapfrog: int = 10
     history : ``"full"`` returns ``samples [nsamples, P]``, ``"moments"`` only ``mean``, ``var``
     track : indices (user order) whose chains are always returned, ``[nsamples, len(track)]``;
         at 1e7 parameters ``history="moments"`` with ``track`` is the intended use
+    prior : a :class:`~multigrad_amd.optim.prior.GaussianPrior` on the (bounded) parameters,
+        not scaled by ``loss_scale``; the MAP of the sampled posterior is
+        ``run_bfgs(prior=prior, prior_weight=1 / loss_scale)``
 
     Returns
     -------
@@ -196,17 +212,29 @@ def hmc_sample(obj, nsamples: int = 1000, warmup: int = 500, nleapfrog: int = 10
         raise ValueError("step_size must be positive")
     comm, sharded = obj.comm, obj.sharded
     n, dev = obj.n_local, obj.device
-    red = DeviceReducer(comm, sharded, dev)  # collective (may connect peer memory)
     layout = obj.vector_layout()
     identity = bool(getattr(layout, "identity", False))
     P = int(layout.P)
     bounds = getattr(obj, "bounds", None)
+    scale = float(loss_scale)
+    pm = pw = None
+    if prior is not None:
+        from .prior import check_prior, penalised_function
+        check_prior(prior, P)  # before any collective
+        if bounds is not None:
+            # the prior is on x: into the wrapped function, before the chain rule to u; the
+            # evaluation below multiplies the whole of it by loss_scale
+            import copy
+            obj = copy.copy(obj)
+            obj.fn = penalised_function(obj.fn, prior, 1.0 / scale)
+        else:
+            pm, pw = prior.local(layout, dev)
+    red = DeviceReducer(comm, sharded, dev)  # collective (may connect peer memory)
     if noise is None:
         rank = comm.rank if (sharded and comm is not None and comm.size > 1) else None
         noise = KeyNoise(seed, rank=rank)
     # with bounds the evaluation below returns U and its gradient themselves; otherwise the
     # loss and its gradient, and loss_scale rides in the kernel's step factor
-    scale = float(loss_scale)
     gscale = 1.0 if bounds is not None else scale
     dev_call = getattr(obj, "device_call", None) if (dev.type == "cuda" and bounds is None) else None
     nfev = 0
@@ -228,9 +256,17 @@ def hmc_sample(obj, nsamples: int = 1000, warmup: int = 500, nleapfrog: int = 10
     if not math.isfinite(U):
         raise ValueError(f"HMC: the potential at the initial position is {U}")
     q_new, g_new, p = torch.empty_like(q), torch.empty_like(g), torch.empty_like(q)
-    ke = torch.zeros(2, dtype=torch.float64, device=dev)
+    # [K, K'] and, with a prior, pen' behind them: one block for the one reduction
+    ke = torch.zeros(2 if pm is None else 3, dtype=torch.float64, device=dev)
     ke0, ke1 = ke[0:1], ke[1:2]
     ws = hmc_workspace(dev)
+    if pm is not None:
+        pen1, pws = ke[2:3], prior_workspace(dev)
+        # the penalty at the start (g_new is scratch here: out = g + 0), summed over the ranks
+        gaussian_prior_grad_(q, g, pm, pw, 0.0, g_new, pen1, pws)
+        U += float(red.reduce(sums=[pen1])[0])
+        if not math.isfinite(U):
+            raise ValueError(f"HMC: the potential at the initial position is {U}")
     # the padding of an engine vector stays where it is: no momentum there
     real = None
     if not identity and n:
@@ -282,7 +318,10 @@ def hmc_sample(obj, nsamples: int = 1000, warmup: int = 500, nleapfrog: int = 10
             z = z * real
         hmc_momentum_(z.contiguous(), im, p, ke0, ws)
         q_new.copy_(q)
-        hmc_leapfrog_(q_new, p, g, im, 0.5 * e * gscale, e)
+        if pm is None:
+            hmc_leapfrog_(q_new, p, g, im, 0.5 * e * gscale, e)
+        else:
+            hmc_leapfrog_prior_(q_new, p, g, im, 0.5 * e * gscale, e, pm, pw, 0.5 * e)
         for i in range(L):
             last = i == L - 1
             if dev_call is not None:
@@ -292,15 +331,23 @@ def hmc_sample(obj, nsamples: int = 1000, warmup: int = 500, nleapfrog: int = 10
                 U_new, gt = evaluate(q_new)
             if last:
                 g_new.copy_(gt)
-                hmc_leapfrog_(q_new, p, g_new, im, 0.5 * e * gscale, 0.0, ke1, ws)
-            else:
+                if pm is None:
+                    hmc_leapfrog_(q_new, p, g_new, im, 0.5 * e * gscale, 0.0, ke1, ws)
+                else:  # b = 0: the penalty it sums is the one at the final position
+                    hmc_leapfrog_prior_(q_new, p, g_new, im, 0.5 * e * gscale, 0.0, pm, pw,
+                                        0.5 * e, ke1, pen1, pws)
+            elif pm is None:
                 hmc_leapfrog_(q_new, p, gt, im, e * gscale, e)
+            else:
+                hmc_leapfrog_prior_(q_new, p, gt, im, e * gscale, e, pm, pw, e)
         # K, K' (summed over the ranks of a sharded objective) and U' in one copy
         if dev_call is not None:
             h = red.reduce(sums=[ke], local=[lt.reshape(-1)[:1]])
-            U_new = scale * float(h[2])
+            U_new = scale * float(h[-1])
         else:
             h = red.reduce(sums=[ke])
+        if pm is not None:
+            U_new += float(h[2])
         dH = (U_new + float(h[1])) - (U + float(h[0]))
         divergent = not math.isfinite(dH) or dH > _MAX_DH
         prob = 0.0 if divergent else math.exp(min(0.0, -dH))
@@ -366,17 +413,24 @@ def hmc_sample(obj, nsamples: int = 1000, warmup: int = 500, nleapfrog: int = 10
 
 def run_hmc(loss_and_grad_fn: Callable, params, nsamples: int = 1000, warmup: int = 500,
             nleapfrog: int = 10, step_size: float = 0.1, param_bounds=None, randkey=0, comm=None,
-            loss_scale: float = 1.0, history: str = "full", track=None, **kw) -> HMCResult:
+            loss_scale: float = 1.0, history: str = "full", track=None, prior=None,
+            **kw) -> HMCResult:
     """HMC for a generic ``loss_and_grad_fn(params) -> (loss, grad)`` (replicated: the
     gradient is the same on every rank).  ``randkey`` (int or key) seeds the sampler's noise;
     with ``param_bounds`` the chain runs in the unbounded coordinates with a flat prior on the
-    bounded parameters.  Other keywords go to :func:`hmc_sample`."""
+    bounded parameters unless ``prior`` (a :class:`~multigrad_amd.optim.prior.GaussianPrior`,
+    on the bounded parameters, not scaled by ``loss_scale``) says otherwise: the chain draws
+    from ``exp(-(loss_scale * loss + prior.penalty(x)))``, whose MAP is
+    ``run_bfgs(prior=prior, prior_weight=1 / loss_scale)``.  Other keywords go to
+    :func:`hmc_sample`."""
     from ..utils.tensors import as_param_tensor
     from .lbfgs import GenericObjective
     from .transforms import Bounds
+    from .prior import check_prior
     x0 = as_param_tensor(params)
+    check_prior(prior, x0.numel())
     bounds = Bounds.from_spec(param_bounds, x0.numel(), device=x0.device, dtype=torch.float32)
     obj = GenericObjective(loss_and_grad_fn, x0, comm=comm, bounds=bounds)
     return hmc_sample(obj, nsamples=nsamples, warmup=warmup, nleapfrog=nleapfrog,
                       step_size=step_size, loss_scale=loss_scale, seed=randkey, history=history,
-                      track=track, **kw)
+                      track=track, prior=prior, **kw)

@@ -237,8 +237,16 @@ def compact_coefficients(SY, YY, Sg, Yg, order):
 
 
 def run_lbfgs_device(loss_and_grad_fn: Callable, params, maxsteps: int = 100, param_bounds=None,
-                     randkey=None, comm=None, history: int = 10, **kw):
+                     randkey=None, comm=None, history: int = 10, prior=None,
+                     prior_weight: float = 1.0, **kw):
     """Device L-BFGS for a generic ``loss_and_grad_fn(params[, randkey])`` (replicated).
+
+    ``prior`` (a :class:`~multigrad_amd.optim.prior.GaussianPrior`) minimises
+    ``loss + prior_weight * prior.penalty(x)`` -- with ``prior_weight = 1 / loss_scale`` the
+    MAP of the posterior that ``run_hmc(prior=..., loss_scale=...)`` samples.  The prior is on
+    the parameters themselves, also with ``param_bounds``.  ``res.fun`` is the minimised
+    objective, ``res.prior_penalty`` the unweighted penalty at ``res.x``, and ``res.hess_inv``
+    approximates the inverse Hessian of likelihood plus prior.
 
     ``hess_inv=True`` (default) returns the inverse-Hessian operator as ``res.hess_inv``
     (it holds the history ring, see :func:`lbfgs_minimize`).  With ``param_bounds`` the
@@ -247,8 +255,15 @@ def run_lbfgs_device(loss_and_grad_fn: Callable, params, maxsteps: int = 100, pa
     from ..utils.random import init_randkey
     from .transforms import Bounds
     from ..utils.tensors import as_param_tensor
+    from .prior import PriorObjective, check_prior, penalised_function, with_penalty
     x0 = as_param_tensor(params)
+    check_prior(prior, x0.numel())
     bounds = Bounds.from_spec(param_bounds, x0.numel(), device=x0.device, dtype=torch.float32)
     fkw = {} if randkey is None else {"randkey": init_randkey(randkey)}
+    if prior is not None and bounds is not None:
+        # the iteration runs in u: the prior goes into the function of x, before the chain rule
+        loss_and_grad_fn = penalised_function(loss_and_grad_fn, prior, prior_weight)
     obj = GenericObjective(loss_and_grad_fn, x0, comm=comm, bounds=bounds, **fkw)
-    return lbfgs_minimize(obj, maxiter=maxsteps, m=history, **kw)
+    if prior is not None and bounds is None:
+        obj = PriorObjective(obj, prior, prior_weight)
+    return with_penalty(lbfgs_minimize(obj, maxiter=maxsteps, m=history, **kw), prior)

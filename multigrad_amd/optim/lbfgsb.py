@@ -490,17 +490,24 @@ def _scan_batch(st, t, g, W, M, theta):
 
 
 def run_lbfgsb_device(loss_and_grad_fn, params, maxsteps: int = 100, param_bounds=None,
-                      randkey=None, comm=None, history: int = 10, **kw):
+                      randkey=None, comm=None, history: int = 10, prior=None,
+                      prior_weight: float = 1.0, **kw):
     """Device L-BFGS-B for a generic ``loss_and_grad_fn(params[, randkey])`` (replicated).
     ``hess_inv=True`` (default) returns the inverse-Hessian operator as ``res.hess_inv``
-    (it holds the history ring, see :func:`lbfgsb_minimize`)."""
+    (it holds the history ring, see :func:`lbfgsb_minimize`).  ``prior`` and ``prior_weight``
+    as for :func:`~multigrad_amd.optim.lbfgs.run_lbfgs_device`: the box-constrained minimum of
+    ``loss + prior_weight * prior.penalty(x)``."""
     from ..utils.random import init_randkey
     from ..utils.tensors import as_param_tensor
+    from .prior import PriorObjective, check_prior, with_penalty
     x0 = as_param_tensor(params)
+    check_prior(prior, x0.numel())
     lo, hi = bounds_arrays(param_bounds, x0.numel())
     fkw = {} if randkey is None else {"randkey": init_randkey(randkey)}
     obj = BoxObjective(loss_and_grad_fn, x0, comm=comm, **fkw)
-    return lbfgsb_minimize(obj, lo, hi, maxiter=maxsteps, m=history, **kw)
+    if prior is not None:
+        obj = PriorObjective(obj, prior, prior_weight)
+    return with_penalty(lbfgsb_minimize(obj, lo, hi, maxiter=maxsteps, m=history, **kw), prior)
 
 
 def bounds_arrays(param_bounds, n: int):
